@@ -7,6 +7,15 @@ lookups with 12 different coordinate sets, exactly the reference's per-forward
 usage (core/raft.py:147, :169-173).  Inputs (fmaps [B,256,H/8,W/8] float32,
 coords = grid + N(0, 4^2) px) are synthetic and resident in HBM before timing.
 
+A plain run (``python bench.py --gpus N --steps K --warmup W``) does only what
+``value`` needs: inputs, the step's graph, the clock warm-up, W warmup steps, K
+timed steps, the pair checksums, and ONE JSON line with ``value`` and
+``ms_per_step`` (the milliseconds one timed step took).  ``--dump-outputs DIR``
+also writes the last timed step's 12 lookup outputs (``dump_outputs`` below).
+Everything else described here — the box calibration, the kernel-timing pass and
+its rooflines, ``value_one_step_per_graph``, the CPU baseline — runs only with
+``--full`` and then fills the same fields of the line as before.
+
 Launch: ``python bench.py [--gpus N --steps K --warmup W]``.  With ``--gpus N > 1``
 and no WORLD_SIZE in the environment, this process starts
 ``torch.distributed.run`` with N ranks (one per GPU, RCCL) as a child before it
@@ -306,6 +315,33 @@ def make_inputs(B, H, W, dtype, seed, dev):
     return f1, f2, coords
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # all files of one --dump-outputs run together (all ranks)
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir: Path, outs, world=1, rank=0):
+    """--dump-outputs: what a caller of the timed step receives from its last run,
+    the step's 12 lookup outputs [B, L*(2r+1)^2, H, W], as float32
+    ``out_dir/lookup_<k>.npy`` (``rank<r>_lookup_<k>.npy`` with several ranks).
+    An output goes whole when all of them fit DUMP_BUDGET_BYTES; otherwise each
+    file holds the same sorted sample of flat indices (numpy default_rng,
+    DUMP_SAMPLE_SEED, without replacement), so that two builds run with the
+    same arguments write comparable files."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    per_file = DUMP_BUDGET_BYTES // (4 * len(outs) * world)
+    numel = outs[0].numel()
+    idx = None
+    if numel > per_file:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        pick = np.sort(rng.choice(numel, per_file, replace=False))
+        idx = torch.from_numpy(pick).to(outs[0].device)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for k, o in enumerate(outs):
+        a = o.detach().float()
+        a = a.reshape(-1)[idx] if idx is not None else a
+        np.save(out_dir / f"{prefix}lookup_{k:02d}.npy", a.cpu().numpy())
+
+
 def _cpu_model() -> str:
     try:
         for line in open("/proc/cpuinfo"):
@@ -425,10 +461,16 @@ def main():
                     help="untimed replays of the step for this long before the W warmup steps: "
                          "the GPU raises its clocks only after ~ms of load (30 timed steps after "
                          "3 warmups read 11 %% low on MI355X)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: box calibration, the kernel-timing pass and "
+                         "its rooflines, value_one_step_per_graph and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's 12 lookup outputs as "
+                         "DIR/lookup_<k>.npy (float32; a fixed seeded sample of large outputs)")
     ap.add_argument("--no-calibration", action="store_true",
-                    help="skip the in-process box calibration (bf16 GEMM + HBM copy)")
+                    help="--full: skip the in-process box calibration (bf16 GEMM + HBM copy)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-impl", default="torch", choices=["torch", "numpy"],
                     help="CPU baseline: torch restatement of core/corr.py (default) or numpy oracle")
     args = ap.parse_args()
@@ -511,7 +553,7 @@ def main():
         # clock warm-up on the step itself (placed after the warm-up it left the
         # driver's 5-replay timed region ~5 % below the same steps re-timed later,
         # round 6: 5,300 vs 5,585 pairs/s on one box)
-        calib = calibrate(dev, stream) if not args.no_calibration else None
+        calib = calibrate(dev, stream) if args.full and not args.no_calibration else None
         # clock warm-up: replay the full step (same work, same outputs) until the
         # chip has been under load for --clock-warmup-s, then the W warmup steps
         t_w = time.perf_counter()
@@ -539,15 +581,19 @@ def main():
         local_sums = state["outs"][-1].double().sum(dim=(1, 2, 3))
         sums = gather_pairs(local_sums, total)
         finite = bool(torch.isfinite(sums).all().item())
+        if args.dump_outputs:
+            # before anything below runs the step's graphs (and so rewrites these) again
+            dump_outputs(Path(args.dump_outputs), state["outs"], world, rank)
 
-        # Kernel-timing pass (outside the timed region): the 12 lookups as one graph,
+        build_ms = look_ms = boundary_ms = one_ms = None
+        # Kernel-timing pass (--full; outside the timed region): the 12 lookups as one graph,
         # replayed back to back after the timed steps (steady clocks): lookup = that
         # time / 12, i.e. one lookup plus its same-stream kernel boundary; build
         # (stage a+b, or the on-the-fly block's pools/layout) = the timed step time
         # - 12 lookups, i.e. the build plus its boundary and the graph launch.
         # Compare with the rocprofv3 kernel durations and the idle time per step of
         # the same command's kernel trace (scripts/trace_gaps.py, profiles/).
-        if args.mode == "graph":
+        if args.full and args.mode == "graph":
             keep = dict(state)            # the step graph's own tensors stay allocated
             cb = state["cb"]              # the last step's block, with its pair set's coords
             g_look = torch.cuda.CUDAGraph()
@@ -597,8 +643,7 @@ def main():
                 del g_one
             boundary_ms = elapsed / args.steps * 1e3 - ITERS * look_ms - build_ms
             del keep, g_build
-        else:
-            one_ms = None
+        elif args.full:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             ev[0].record(stream)
             build()
@@ -634,6 +679,7 @@ def main():
             "vs_baseline": None,
             "value_one_step_per_graph": (round(total / (one_ms * 1e-3), 3) if one_ms else None),
             "dtype": dtype,
+            "full": args.full,
             "data": "synthetic (torch.randn fmaps, coords = grid + N(0,4^2) px)",
             "config": {
                 "workload": f"{'CorrBlock' if args.block == 'corr' else 'AlternateCorrBlock'} "
@@ -645,7 +691,7 @@ def main():
                                 f"lookups each); {args.steps // G} replays"
                                 if args.mode == "graph" else "eager launches"),
                 "steps_per_graph": G, "pair_sets": len({id(t[0]) for t in sets}),
-                "kernel_timing": timing,
+                "kernel_timing": timing if args.full else None,
                 "clock_warmup": f"{n_clock} untimed step replays ({args.clock_warmup_s} s) before "
                                 f"the {args.warmup} warmup steps",
             },
@@ -658,7 +704,7 @@ def main():
                 "first": [round(float(v), 3) for v in sums[:4].tolist()],
             },
         }
-        if args.block == "corr":
+        if args.full and args.block == "corr":
             kname, mfma_per_flop, pipe_peak, mfma_dtype = build_kernel(dtype, H, W)
             # achieved = ALGORITHMIC flops (2*B*N^2*D) per launch / launch time.
             # Ceiling = the dense MFMA peak of the arithmetic actually run: bf16 fmaps
@@ -699,7 +745,7 @@ def main():
                 "traffic": l_traffic, "traffic_source": l_src,
                 "avg_launch_us": round(look_ms * 1e3, 2),
             }
-        else:
+        elif args.full:
             # on-the-fly lookups: (2r+2)^2 window dot products of length D per query
             # and level, f32-class arithmetic (SURVEY.md §8(d) stage d), priced at
             # the f32 peak; the default kernel runs them as f16-pair split MFMA GEMMs.
@@ -733,7 +779,7 @@ def main():
                 "pool_and_layout_us_per_step": round(build_ms * 1e3, 2),
                 "step_boundary_us": round(boundary_ms * 1e3, 2),
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(H, W, args.cpu_seconds, args.cpu_impl)
         print(json.dumps(res), flush=True)
     if world > 1:

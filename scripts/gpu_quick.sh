@@ -23,6 +23,6 @@ fi
 i=0
 for A in "$@"; do
   i=$((i+1))
-  run bench$i 300 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline $A
+  run bench$i 300 python -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline $A
 done
 echo "== done"

@@ -8,7 +8,7 @@ shift || true
 OUT=$PWD/gpurun_out/$TAG/pmc
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH=(python -u bench.py --steps 4 --warmup 1 --mode eager --no-cpu-baseline "$@")
+BENCH=(python -u bench.py --full --steps 4 --warmup 1 --mode eager --no-cpu-baseline "$@")
 
 timeout -s KILL 60 rocprofv3 -L > "$OUT/counters_list.txt" 2>&1
 echo "counter list rc=$?"
