@@ -88,7 +88,8 @@ enum dxr_status {
 
 enum dxr_dtype {
   DXR_F32 = 0,
-  DXR_BF16 = 1          /* storage as IEEE bfloat16 bit patterns (uint16) */
+  DXR_BF16 = 1,         /* storage as IEEE bfloat16 bit patterns (uint16) */
+  DXR_F16 = 2           /* IEEE float16 fmaps: an in_dtype of the pyramid builds only */
 };
 
 enum dxr_layout {
@@ -120,7 +121,7 @@ int64_t dxr_pyramid_level_offset(int64_t B, int64_t H, int64_t W, int level);
  * Stage (a)+(b): all-pairs correlation fmap1^T . fmap2 / divisor and its
  * avg-pool pyramid, written in one pass (pooling fused into the MFMA epilogue).
  *   fmap1, fmap2 : [B, D, H, W] (fmap_layout DXR_NCHW) or [B, H, W, D]
- *                  (DXR_NHWC), dtype in_dtype (DXR_F32 or DXR_BF16)
+ *                  (DXR_NHWC), dtype in_dtype (DXR_F32, DXR_BF16 or DXR_F16)
  *   divisor      : the reference divides by sqrt(D) (core/corr.py:60)
  *   pyramid      : dxr_pyramid_numel(B,H,W,num_levels) elements of pyr_dtype
  *                  (levels beyond 4 need pyr_dtype DXR_F32)
@@ -139,6 +140,19 @@ int64_t dxr_pyramid_level_offset(int64_t B, int64_t H, int64_t W, int level);
  * v_mfma_f32_32x32x2_f32 is used.  Pyramid stores are write-through (sc1).
  * DXR_BF16 inputs use bf16 MFMA with f32 accumulation.  NHWC and NCHW inputs
  * of the same values give bit-identical pyramids.
+ * DXR_F16 inputs (float16 fmaps, what autocast encoders emit under
+ * --mixed_precision) run the LDS-DMA build on f16 records: one
+ * v_mfma_f32_32x32x16_f16 product per channel pair, f32 accumulation, no
+ * scales, into a DXR_F32 pyramid.  Every f16 is an f32 and f16 x f16 products
+ * are exact in f32, so the result is the f32 matmul of the widened fmaps to
+ * accumulation rounding (f32 class; inf/NaN propagate through the MFMA).  It
+ * needs D % 32 == 0, D * H * W < 2^30, a 16-byte aligned pyramid and either
+ * channels-last fmaps with 16-byte aligned pixel rows or, for NCHW fmaps, the
+ * workspace of dxr_corr_pyramid_build_ws; every other valid DXR_F16 request
+ * (also a DXR_BF16 pyramid and DXR_BUILD_EXACT_F32) returns DXR_EUNSUPPORTED
+ * and the caller widens the fmaps to f32.  DXR_F16 is no pyr_dtype, and no
+ * dtype of any other entry point (dxr_corr_volume: DXR_EUNSUPPORTED;
+ * dxr_transpose moves f16 fmaps as DXR_BF16, any 16-bit pattern).
  *
  * Kernels by request (both build entry points; tests/test_gpu_parity.py
  * test_build_kernel_by_request runs each one by name against the oracle):
@@ -154,6 +168,10 @@ int64_t dxr_pyramid_level_offset(int64_t B, int64_t H, int64_t W, int level);
  *   bf16 NHWC, D % 32 == 0              corr_build_dma_kernel (rows read in place)
  *   bf16 NCHW, no workspace, W % 4 == 0 corr_build_bf16_q2_kernel
  *   bf16 otherwise                      corr_build_bf16_kernel (one query block)
+ *   f16 NCHW, workspace, D % 32 == 0    pack_bf16_kernel + corr_build_dma_kernel
+ *                                        (f16 records, f32 pyramid)
+ *   f16 NHWC, D % 32 == 0               corr_build_dma_kernel (rows read in place)
+ *   f16 otherwise                       none: DXR_EUNSUPPORTED
  */
 int dxr_corr_pyramid_build(const void* fmap1, const void* fmap2, int in_dtype,
                            int fmap_layout, int64_t B, int64_t D, int64_t H,
@@ -165,7 +183,8 @@ int dxr_corr_pyramid_build(const void* fmap1, const void* fmap2, int in_dtype,
  * Bytes of device workspace dxr_corr_pyramid_build_ws uses for B pairs of
  * D x H x W fmaps of in_dtype (0: that request needs none; -1: bad geometry):
  * f32 with D % 16 == 0 the pre-split operands, bf16 with D % 32 == 0 the pack
- * pass's blocked copies of NCHW fmaps (channels-last bf16 fmaps need none).
+ * pass's blocked copies of NCHW fmaps (channels-last bf16 fmaps need none);
+ * f16 as bf16 (the same 16-bit pack pass).
  * ABI 6.
  */
 int64_t dxr_build_workspace_bytes(int in_dtype, int64_t B, int64_t D, int64_t H,
@@ -190,7 +209,8 @@ int64_t dxr_build_workspace_bytes(int in_dtype, int64_t B, int64_t D, int64_t H,
  * pixel rows.  With DXR_BF16 NCHW fmaps (D % 32 == 0) a pack pass copies the
  * operands into 64-byte records of 32 channels per pixel and the bf16 build
  * runs the same LDS-DMA K loop on them — the workspace-less bf16 build's
- * pyramid bit for bit.  A NULL or short workspace runs dxr_corr_pyramid_build.
+ * pyramid bit for bit; DXR_F16 NCHW fmaps take the same pack pass and the f16
+ * record build (above).  A NULL or short workspace runs dxr_corr_pyramid_build.
  * Replaces the same reference lines: core/corr.py:52-60 + :21-27.  ABI 6.
  */
 int dxr_corr_pyramid_build_ws(const void* fmap1, const void* fmap2, int in_dtype,

@@ -18,7 +18,7 @@ LIB_PATH = Path(__file__).resolve().with_name("libdexiraft_corr.so")
 ABI_VERSION = 10
 
 DXR_OK, DXR_EINVAL, DXR_EUNSUPPORTED, DXR_EHIP = 0, 1, 2, -1
-DXR_F32, DXR_BF16 = 0, 1
+DXR_F32, DXR_BF16, DXR_F16 = 0, 1, 2   # DXR_F16: an in_dtype of the pyramid builds only
 DXR_NCHW, DXR_NHWC = 0, 1
 DXR_BUILD_AUTO, DXR_BUILD_EXACT_F32 = 0, 1
 

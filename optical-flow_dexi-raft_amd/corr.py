@@ -21,8 +21,8 @@ Differences from the reference, all loud:
   * host (CPU) tensors raise ``RuntimeError`` instead of running on the CPU;
   * coords that require grad raise ``NotImplementedError`` (the reference
     detaches them, core/raft.py:170; no grid gradient is implemented), as do
-    bfloat16 fmaps that require grad and AlternateCorrBlock inputs that require
-    grad (the reference's alt_cuda_corr output carries no autograd graph).
+    bfloat16 or float16 fmaps that require grad and AlternateCorrBlock inputs
+    that require grad (the reference's alt_cuda_corr output carries no autograd graph).
 """
 from __future__ import annotations
 
@@ -327,11 +327,13 @@ def _channels_last(t: torch.Tensor) -> bool:
 
 
 def _dtype_code(t: torch.Tensor) -> int:
+    """Element code of ``dxr_transpose`` (a bit-exact move: float16 goes as any
+    16-bit pattern, DXR_BF16)."""
     if t.dtype == torch.float32:
         return nat.DXR_F32
-    if t.dtype == torch.bfloat16:
+    if t.dtype in (torch.bfloat16, torch.float16):
         return nat.DXR_BF16
-    raise RuntimeError(f"fmaps must be float32 or bfloat16, got {t.dtype}")
+    raise RuntimeError(f"fmaps must be float32, bfloat16 or float16, got {t.dtype}")
 
 
 def _nchw(t: torch.Tensor) -> torch.Tensor:
@@ -454,6 +456,16 @@ class CorrBlock:
     exact-f32 MFMA.  The pyramid is stored in f32; bf16 fmaps build a bf16
     pyramid on bf16 MFMA.  It lives in one paged buffer (``_buf``);
     ``corr_pyramid`` gives the reference-layout levels on demand.
+
+    float16 fmaps (what the encoders emit under ``--mixed_precision``; the
+    reference widens them with ``.float()``, core/raft.py:139-142) are taken as
+    they are: the same LDS-DMA build on f16 records runs ONE f16 MFMA product
+    per channel pair, with no split pass and no scales, into an f32 pyramid.
+    Every f16 value is an f32 value and f16 x f16 products are exact in the f32
+    accumulator, so this is the reference's f32 matmul on the widened fmaps to
+    accumulation rounding (f32 class, unlike the bf16 mode).  Shapes that build
+    does not cover (D % 32 != 0) are widened here and take the f32 path.
+    Inference only: float16 fmaps that require grad raise, as bfloat16 ones do.
     """
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
@@ -471,10 +483,12 @@ class CorrBlock:
             in_dt, pyr_dt, pyr_torch = nat.DXR_F32, nat.DXR_F32, torch.float32
         elif fmap1.dtype == torch.bfloat16:
             in_dt, pyr_dt, pyr_torch = nat.DXR_BF16, nat.DXR_BF16, torch.bfloat16
+        elif fmap1.dtype == torch.float16:
+            in_dt, pyr_dt, pyr_torch = nat.DXR_F16, nat.DXR_F32, torch.float32
         else:
-            raise RuntimeError(f"fmaps must be float32 or bfloat16, got {fmap1.dtype}")
-        if pyr_dt != nat.DXR_F32:
-            _require_no_grad(fmap1, fmap2, what="bfloat16 fmaps")
+            raise RuntimeError(f"fmaps must be float32, bfloat16 or float16, got {fmap1.dtype}")
+        if in_dt != nat.DXR_F32:
+            _require_no_grad(fmap1, fmap2, what=f"{str(fmap1.dtype)[6:]} fmaps")
         self._geom = (B, D, H, W)
         self._pyr_dt = pyr_dt
         self._device = fmap1.device
@@ -484,6 +498,12 @@ class CorrBlock:
         grad = _wants_grad(fmap1, fmap2)
         self._in_dt = in_dt
         f1, f2, st = self._launch_build(fmap1, fmap2, grad)
+        if st == nat.DXR_EUNSUPPORTED and in_dt == nat.DXR_F16:
+            # a shape the f16 record build does not cover (D % 32 != 0): widen
+            # exactly, as the reference does (core/raft.py:139-142), and take the
+            # f32 path; the memory format is kept
+            self._in_dt = nat.DXR_F32
+            f1, f2, st = self._launch_build(fmap1.float(), fmap2.float(), grad)
         nat.check(st, "CorrBlock build (dxr_corr_pyramid_build_ws)")
         self._level_sizes = sizes
         self._ref_pyramid = None
@@ -517,10 +537,10 @@ class CorrBlock:
         if not grad and _channels_last(fmap1) and _channels_last(fmap2):
             # channels-last fmaps: read in place by the
             # build's NHWC operand loads (f32: the pre-split pass, into the
-            # workspace; bf16: the DMA build reads the rows directly and needs no
-            # workspace), no layout pass
+            # workspace; bf16 / f16: the DMA build reads the rows directly and
+            # needs no workspace), no layout pass
             f1, f2 = fmap1, fmap2
-            st = launch(f1, f2, nat.DXR_NHWC, with_ws=self._in_dt != nat.DXR_BF16)
+            st = launch(f1, f2, nat.DXR_NHWC, with_ws=self._in_dt == nat.DXR_F32)
         if st == nat.DXR_EUNSUPPORTED:
             if grad:
                 f1, f2 = fmap1.contiguous(), fmap2.contiguous()   # tracked by autograd
@@ -661,6 +681,8 @@ class AlternateCorrBlock:
     fly form's bit for bit (``coarse_first_level`` None: no volumes).  As in the
     reference, the constructor pools ``num_levels`` times, so fmaps smaller than
     2^num_levels in either dimension raise (core/corr.py:69-71).
+    bfloat16 and float16 fmaps are widened exactly to float32 first (the
+    reference's own cast, core/raft.py:139-142).
     """
 
     # Which levels are precomputed (round 6, bench.py --block alt, profiles/r06/experiments/
@@ -682,14 +704,15 @@ class AlternateCorrBlock:
         B, D, H, W = _fmap_geometry(fmap1, fmap2)
         _require_no_grad(fmap1, fmap2, what="AlternateCorrBlock (the reference's alt_cuda_corr "
                                             "output carries no autograd graph, core/corr.py:85-88)")
-        if fmap1.dtype == torch.bfloat16:
+        if fmap1.dtype in (torch.bfloat16, torch.float16):
             # The reference computes in float32 (core/raft.py:139-142 casts the
-            # fmaps; alt_cuda_corr is float-only): bf16 encoder outputs are widened
-            # exactly, keeping their memory format (channels-last stays a free view).
+            # fmaps; alt_cuda_corr is float-only): bf16 / f16 encoder outputs are
+            # widened exactly, keeping their memory format (channels-last stays a
+            # free view).
             fmap1, fmap2 = fmap1.float(), fmap2.float()
         elif fmap1.dtype != torch.float32:
-            raise RuntimeError(f"AlternateCorrBlock expects float32 or bfloat16 fmaps, got "
-                               f"{fmap1.dtype}")
+            raise RuntimeError(f"AlternateCorrBlock expects float32, bfloat16 or float16 fmaps, "
+                               f"got {fmap1.dtype}")
         if not isinstance(num_levels, int) or num_levels < 1:
             raise ValueError(f"num_levels must be a positive int, got {num_levels!r}")
         if not isinstance(radius, int) or radius < 0:

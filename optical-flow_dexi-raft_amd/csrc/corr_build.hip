@@ -1459,6 +1459,11 @@ __global__ __launch_bounds__(PX * 16) void split_pairs_kernel(const float* __res
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 
+// Operand kind of the DMA build (corr_build_dma_kernel, dma_quarter): scaled f16
+// pairs of f32 fmaps (split_pairs_kernel), or 64-byte records of 32 consecutive
+// channels of a pixel, bf16 or f16, as 16-bit fmaps hold them.
+constexpr int DMA_PAIRS = 0, DMA_BF16 = 1, DMA_F16 = 2;
+
 // Pyramid store policy of the DMA builds' epilogue (paged_epilogue EX), picked per
 // launch (EXF; dma_stream_out): wave-private staging + write-through buffer stores (5),
 // or non-temporal stores (3) for pyramids far beyond the Infinity Cache.
@@ -1591,7 +1596,7 @@ __device__ __forceinline__ void dma_scales(const BuildGeom& g, const int* __rest
 // loop is a quarter of the MFMA work at the same per-step latency, so the
 // last, partial dispatch round of whole units (1,568 units on 512 slots at
 // Sintel B=1: 32 units alone for a whole unit time) becomes 128 short ones.
-template <typename OT, bool DIV, bool BF, int EXF = 5>
+template <typename OT, bool DIV, int OPK, int EXF = 5>
 __device__ __forceinline__ void dma_quarter(unsigned char* smem, const uint8_t* __restrict__ sp1,
                                             const uint8_t* __restrict__ sp2,
                                             const int* __restrict__ ex1,
@@ -1599,6 +1604,7 @@ __device__ __forceinline__ void dma_quarter(unsigned char* smem, const uint8_t* 
                                             const float* __restrict__ f1,
                                             const float* __restrict__ f2, int ps, int ks, int pstr,
                                             int kstr, const BuildGeom& g) {
+  constexpr bool BF = OPK != DMA_PAIRS;   // record operands: 32 channels per stage, no scales
   int* const sexp = reinterpret_cast<int*>(smem + DMA_LDS_RING);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1674,13 +1680,20 @@ __device__ __forceinline__ void dma_quarter(unsigned char* smem, const uint8_t* 
     __builtin_amdgcn_sched_barrier(0);
     if (kk + 2 < nk) dma(kk + 2);
     const unsigned char* st = smem + (kk % DMA_RING) * DMA_STAGE;
-    if constexpr (BF) {
+    if constexpr (OPK == DMA_BF16) {
       const bf8v q0v = *reinterpret_cast<const bf8v*>(st + qh_off);
       const bf8v q1v = *reinterpret_cast<const bf8v*>(st + ql_off);
       const bf8v t0v = *reinterpret_cast<const bf8v*>(st + th_off);
       const bf8v t1v = *reinterpret_cast<const bf8v*>(st + tl_off);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t0v, q0v, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t1v, q1v, acc, 0, 0, 0);
+    } else if constexpr (OPK == DMA_F16) {
+      const h8v q0v = *reinterpret_cast<const h8v*>(st + qh_off);
+      const h8v q1v = *reinterpret_cast<const h8v*>(st + ql_off);
+      const h8v t0v = *reinterpret_cast<const h8v*>(st + th_off);
+      const h8v t1v = *reinterpret_cast<const h8v*>(st + tl_off);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(t0v, q0v, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(t1v, q1v, acc, 0, 0, 0);
     } else {
       const h8v qh = *reinterpret_cast<const h8v*>(st + qh_off);
       const h8v ql = *reinterpret_cast<const h8v*>(st + ql_off);
@@ -1727,25 +1740,34 @@ __device__ __forceinline__ void dma_quarter(unsigned char* smem, const uint8_t* 
 // NaN propagates).  Grid: dma_grid(g, B, stream) — [0, g.nmain) whole units in the
 // XCD-banded order (page_coord<true, 2>), then the tail's quarter units.
 //
-// BF (bf16 mode, C3): the same K loop on bf16 operand records — a 64-B record
-// is 32 consecutive channels of one pixel (k 0-7 | 8-15 | 16-23 | 24-31 in the
-// four 16-B slots), so a stage is two 16-deep bf16 MFMA steps (slots kh, then
-// 2 + kh), accumulated in the order of corr_build_bf16_q2_kernel: the same
-// pages bit for bit.  Records come straight from channels-last bf16 fmaps
-// (pixel stride D * 2 B, stage stride 64 B) or from the pack pass's blocked copy
-// of NCHW fmaps (pixel stride 64 B, stage stride N * 64 B): `pstr` / `kstr`.
-// No scales, no non-finite fallback (bf16 MFMA propagates inf/NaN itself), and
-// the bf16 build's non-temporal pyramid stores.
-template <typename OT, bool DIV, bool BF = false, int EXF = 5>
+// OPK = DMA_BF16 (bf16 mode, C3): the same K loop on bf16 operand records — a
+// 64-B record is 32 consecutive channels of one pixel (k 0-7 | 8-15 | 16-23 |
+// 24-31 in the four 16-B slots), so a stage is two 16-deep bf16 MFMA steps
+// (slots kh, then 2 + kh), accumulated in the order of
+// corr_build_bf16_q2_kernel: the same pages bit for bit.  Records come straight
+// from channels-last bf16 fmaps (pixel stride D * 2 B, stage stride 64 B) or
+// from the pack pass's blocked copy of NCHW fmaps (pixel stride 64 B, stage
+// stride N * 64 B): `pstr` / `kstr`.  No scales, no non-finite fallback (bf16
+// MFMA propagates inf/NaN itself).
+//
+// OPK = DMA_F16 (float16 fmaps, mixed precision): the record mode on f16
+// records and v_mfma_f32_32x32x16_f16 — one product per channel pair where the
+// pair mode, given values that started as f16 (lo = 0), runs three.  Every f16
+// is an f32 and f16 x f16 products are exact in the f32 accumulator, so this is
+// the f32 matmul of the widened fmaps to accumulation rounding: f32 class, an
+// f32 pyramid, no scales (the smallest product, 2^-48, is a normal f32) and no
+// non-finite recompute (the f16 MFMA propagates inf/NaN itself).
+template <typename OT, bool DIV, int OPK = DMA_PAIRS, int EXF = 5>
 __global__ __launch_bounds__(2 * NT, 4) void corr_build_dma_kernel(
     const uint8_t* __restrict__ sp1, const uint8_t* __restrict__ sp2, const int* __restrict__ ex1,
     const int* __restrict__ ex2, OT* __restrict__ pyr, const float* __restrict__ f1,
     const float* __restrict__ f2, int ps, int ks, int pstr, int kstr, BuildGeom g) {
   static_assert(WAVES * 16 * P0 * 4 * 2 <= DMA_LDS_RING, "the epilogue staging aliases the ring");
+  constexpr bool BF = OPK != DMA_PAIRS;   // record operands: 32 channels per stage, no scales
   // one LDS array (cdna_hip_programming.md §5 item 4(a))
   __shared__ __attribute__((aligned(16))) unsigned char smem[DMA_LDS_BYTES];
   if (blockIdx.x >= (unsigned)g.nmain) {
-    dma_quarter<OT, DIV, BF, EXF>(smem, sp1, sp2, ex1, ex2, pyr, f1, f2, ps, ks, pstr, kstr, g);
+    dma_quarter<OT, DIV, OPK, EXF>(smem, sp1, sp2, ex1, ex2, pyr, f1, f2, ps, ks, pstr, kstr, g);
     return;
   }
   int* const sexp = reinterpret_cast<int*>(smem + DMA_LDS_RING);
@@ -1830,7 +1852,22 @@ __global__ __launch_bounds__(2 * NT, 4) void corr_build_dma_kernel(
     __builtin_amdgcn_sched_barrier(0);
     if (kk + 2 < nk) dma(kk + 2);
     const unsigned char* st = smem + (kk % DMA_RING) * DMA_STAGE;
-    if constexpr (BF) {
+    if constexpr (OPK == DMA_F16) {
+      // the bf16 records' stage on the f16 MFMA: k 0-15 for every tile, then k 16-31
+      const h8v q0v = *reinterpret_cast<const h8v*>(st + qh_off);
+      const h8v q1v = *reinterpret_cast<const h8v*>(st + ql_off);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const h8v t0v = *reinterpret_cast<const h8v*>(st + th_off + t * 2048);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(t0v, q0v, FIRST ? f32x16{} : acc[t], 0, 0,
+                                                        0);
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const h8v t1v = *reinterpret_cast<const h8v*>(st + tl_off + t * 2048);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(t1v, q1v, acc[t], 0, 0, 0);
+      }
+    } else if constexpr (OPK == DMA_BF16) {
       // k 0-15 of the stage for every tile, then k 16-31 (the q2 kernel's order)
       const bf8v q0v = *reinterpret_cast<const bf8v*>(st + qh_off);
       const bf8v q1v = *reinterpret_cast<const bf8v*>(st + ql_off);
@@ -2191,15 +2228,15 @@ bool dma_stream_out(const BuildGeom& g, int B) {
   return pyr_bytes > 512.0 * (1 << 20);
 }
 
-// Launch corr_build_dma_kernel<OT, DIV, BF, EXF> with DIV from g.recip and EXF
+// Launch corr_build_dma_kernel<OT, DIV, OPK, EXF> with DIV from g.recip and EXF
 // from dma_stream_out.
-template <typename OT, bool BF, typename... A>
+template <typename OT, int OPK, typename... A>
 void launch_dma_kernel(const dim3& rg, const BuildGeom& g, int B, hipStream_t stream, A... args) {
   const bool so = dma_stream_out<OT>(g, B);
   auto go = [&](auto div_tag, auto ex_tag) {
     constexpr bool DV = decltype(div_tag)::value;
     constexpr int EXF = decltype(ex_tag)::value;
-    hipLaunchKernelGGL((corr_build_dma_kernel<OT, DV, BF, EXF>), rg, dim3(2 * NT), 0, stream,
+    hipLaunchKernelGGL((corr_build_dma_kernel<OT, DV, OPK, EXF>), rg, dim3(2 * NT), 0, stream,
                        args..., g);
   };
   using T5 = std::integral_constant<int, 5>;
@@ -2242,20 +2279,21 @@ int launch_dma(const float* f1, const float* f2, OT* pyr, BuildGeom g, int B, vo
   if (st != DXR_OK) return st;
   const dim3 rg = dma_grid(g, B, stream, tail);
   const int ps = NHWC ? g.D : 1, ks = NHWC ? 1 : g.N;   // fallback operand strides
-  launch_dma_kernel<OT, false>(rg, g, B, stream, (const uint8_t*)sp1, (const uint8_t*)sp2,
+  launch_dma_kernel<OT, DMA_PAIRS>(rg, g, B, stream, (const uint8_t*)sp1, (const uint8_t*)sp2,
                                (const int*)e1, (const int*)e2, pyr, f1, f2, ps, ks, 64, g.N * 64);
   return dxr::launch_status();
 }
 
-// bf16 operand records by LDS-DMA (corr_build_dma_kernel<.., BF>): channels-last
-// bf16 fmaps are read in place (pixel stride D * 2 B, stage stride 64 B).
-template <typename OT>
+// 16-bit operand records by LDS-DMA (corr_build_dma_kernel<.., OPK>, OPK =
+// DMA_BF16 or DMA_F16): channels-last bf16 / f16 fmaps are read in place (pixel
+// stride D * 2 B, stage stride 64 B).
+template <typename OT, int OPK = DMA_BF16>
 int launch_dma_bf16_nhwc(const uint16_t* f1, const uint16_t* f2, OT* pyr, BuildGeom g, int B,
                          hipStream_t stream, int tail = DMA_TAIL_DEFAULT) {
   const dim3 rg = dma_grid(g, B, stream, tail);
   const uint8_t* a = reinterpret_cast<const uint8_t*>(f1);
   const uint8_t* c = reinterpret_cast<const uint8_t*>(f2);
-  launch_dma_kernel<OT, true>(rg, g, B, stream, a, c, (const int*)nullptr, (const int*)nullptr, pyr,
+  launch_dma_kernel<OT, OPK>(rg, g, B, stream, a, c, (const int*)nullptr, (const int*)nullptr, pyr,
                               (const float*)nullptr, (const float*)nullptr, 0, 0, g.D * 2, 64);
   return dxr::launch_status();
 }
@@ -2320,7 +2358,7 @@ long long bf16_pack_bytes(long long B, long long D, long long H, long long W) {
 
 // NCHW bf16 fmaps with a workspace: pack pass + the bf16 DMA build
 // (blocked records: pixel stride 64 B, stage stride N * 64 B).
-template <typename OT>
+template <typename OT, int OPK = DMA_BF16>
 int launch_dma_bf16_nchw(const uint16_t* f1, const uint16_t* f2, OT* pyr, BuildGeom g, int B,
                          void* ws, hipStream_t stream, int tail = DMA_TAIL_DEFAULT) {
   const long long half = align256((long long)B * g.D * g.N * 2);
@@ -2335,7 +2373,7 @@ int launch_dma_bf16_nchw(const uint16_t* f1, const uint16_t* f2, OT* pyr, BuildG
   int st = dxr::launch_status();
   if (st != DXR_OK) return st;
   const dim3 rg = dma_grid(g, B, stream, tail);
-  launch_dma_kernel<OT, true>(rg, g, B, stream, (const uint8_t*)o1, (const uint8_t*)o2,
+  launch_dma_kernel<OT, OPK>(rg, g, B, stream, (const uint8_t*)o1, (const uint8_t*)o2,
                               (const int*)nullptr, (const int*)nullptr, pyr, (const float*)nullptr,
                               (const float*)nullptr, 0, 0, 64, g.N * 64);
   return dxr::launch_status();
@@ -2384,7 +2422,7 @@ int check_build_args(const void* fmap1, const void* fmap2, int in_dtype, int64_t
                      float divisor, const void* out, int out_dtype) {
   if (D < 1 || D > (1 << 20) || !(divisor == divisor) || divisor == 0.f) return DXR_EINVAL;
   if (B > 65535) return DXR_EINVAL;
-  if ((in_dtype != DXR_F32 && in_dtype != DXR_BF16) ||
+  if ((in_dtype != DXR_F32 && in_dtype != DXR_BF16 && in_dtype != DXR_F16) ||
       (out_dtype != DXR_F32 && out_dtype != DXR_BF16))
     return DXR_EINVAL;
   if (B == 0) return DXR_OK;
@@ -2403,6 +2441,19 @@ extern "C" int dxr_avg_pool2x2(const float* in, float* out, int64_t planes, int6
 }
 
 namespace {
+// Levels beyond the fused four: plain pooling passes, level l from level l-1.
+int pool_extra_levels(float* pyr, const dxr::Levels& L, int64_t B, int64_t H, int64_t W,
+                      hipStream_t stream) {
+  for (int l = dxr::TILED_LEVELS; l < L.n; ++l) {
+    const long long total = B * H * W * (long long)L.h[l] * L.w[l];
+    hipLaunchKernelGGL(pool_level_kernel, dim3(grid_for(total)), dim3(256), 0, stream, pyr,
+                       L.lay[l - 1], L.lay[l], (int)B, (int)(H * W));
+    const int st = dxr::launch_status();
+    if (st != DXR_OK) return st;
+  }
+  return DXR_OK;
+}
+
 int pyramid_build(const void* fmap1, const void* fmap2, int in_dtype, int fmap_layout, int64_t B,
                   int64_t D, int64_t H, int64_t W, int num_levels, float divisor, void* pyramid,
                   int pyr_dtype, int algo, void* workspace, int64_t workspace_bytes,
@@ -2417,6 +2468,30 @@ int pyramid_build(const void* fmap1, const void* fmap2, int in_dtype, int fmap_l
   if (L.n > dxr::TILED_LEVELS && pyr_dtype != DXR_F32) return DXR_EUNSUPPORTED;
   if (algo == DXR_BUILD_EXACT_F32 && in_dtype != DXR_F32) return DXR_EUNSUPPORTED;
   const BuildGeom g = make_geom(D, H, W, divisor, L);
+  if (in_dtype == DXR_F16) {
+    // float16 operands (mixed-precision encoders): the DMA build on f16 records,
+    // one MFMA product per channel pair, into an f32 pyramid.  Channels-last
+    // fmaps are read in place; NCHW fmaps go through the 16-bit pack pass into the
+    // workspace.  The bf16 DMA forms' limits (D % 32 == 0, D * N * 2 < 2^31 per
+    // pair, 16-byte alignment).  Anything else is unsupported: callers widen to
+    // f32, as the reference does (core/raft.py:139-142).
+    if (pyr_dtype != DXR_F32 || D % 32 != 0 || D * H * W >= (1LL << 30) || !aligned16(pyramid))
+      return DXR_EUNSUPPORTED;
+    const uint16_t* f1 = static_cast<const uint16_t*>(fmap1);
+    const uint16_t* f2 = static_cast<const uint16_t*>(fmap2);
+    float* pf = static_cast<float*>(pyramid);
+    int st16;
+    if (fmap_layout == DXR_NHWC) {
+      if (!aligned16(fmap1) || !aligned16(fmap2)) return DXR_EUNSUPPORTED;
+      st16 = launch_dma_bf16_nhwc<float, DMA_F16>(f1, f2, pf, g, (int)B, stream);
+    } else {
+      if (workspace == nullptr || !aligned16(workspace) ||
+          workspace_bytes < bf16_pack_bytes(B, D, H, W))
+        return DXR_EUNSUPPORTED;
+      st16 = launch_dma_bf16_nchw<float, DMA_F16>(f1, f2, pf, g, (int)B, workspace, stream);
+    }
+    return st16 != DXR_OK ? st16 : pool_extra_levels(pf, L, B, H, W, stream);
+  }
   int st = PROCEED;
   // f32 operands with a workspace: pre-split f16 pairs + the LDS-DMA build
   // (any W; D % 16 == 0; NHWC rows 16-byte aligned).
@@ -2496,23 +2571,15 @@ int pyramid_build(const void* fmap1, const void* fmap2, int in_dtype, int fmap_l
              : launch_build_bf16(vec, f1, f2, static_cast<uint16_t*>(pyramid), g, (int)B, stream);
   }
   if (st != DXR_OK) return st;
-  float* pyr = static_cast<float*>(pyramid);
-  // Levels beyond the fused four: plain pooling passes, level l from level l-1.
-  for (int l = dxr::TILED_LEVELS; l < L.n; ++l) {
-    const long long total = B * H * W * (long long)L.h[l] * L.w[l];
-    hipLaunchKernelGGL(pool_level_kernel, dim3(grid_for(total)), dim3(256), 0, stream, pyr,
-                       L.lay[l - 1], L.lay[l], (int)B, (int)(H * W));
-    st = dxr::launch_status();
-    if (st != DXR_OK) return st;
-  }
-  return DXR_OK;
+  return pool_extra_levels(static_cast<float*>(pyramid), L, B, H, W, stream);
 }
 }  // namespace
 
 extern "C" int64_t dxr_build_workspace_bytes(int in_dtype, int64_t B, int64_t D, int64_t H,
                                              int64_t W) {
   if (B < 0 || D < 1 || H < 1 || W < 1 || H * W > (1LL << 30)) return -1;
-  if (in_dtype == DXR_BF16) return D % 32 == 0 ? bf16_pack_bytes(B, D, H, W) : 0;
+  if (in_dtype == DXR_BF16 || in_dtype == DXR_F16)   // the 16-bit pack pass of NCHW fmaps
+    return D % 32 == 0 ? bf16_pack_bytes(B, D, H, W) : 0;
   if (in_dtype != DXR_F32 || D % 16 != 0) return 0;
   return dma_workspace_bytes(B, D, H, W);
 }
