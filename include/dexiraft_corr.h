@@ -259,6 +259,8 @@ int dxr_corr_lookup(const void* pyramid, int pyr_dtype,
  * (dxr_pyramid_numel; the caller zero-fills it once and may accumulate several
  * lookups into it).  grad_out: [B, num_levels*(2r+1)^2, H, W] float32.  No
  * coordinate gradient (the reference detaches coords, core/raft.py:170).
+ * Cells the lookup does not tap keep their bits, and far / non-finite queries
+ * add nothing, as grid_sample's backward does (tests/test_gpu_lookup_backward.py).
  */
 int dxr_corr_lookup_backward(const float* coords, const float* grad_out,
                              int64_t B, int64_t H, int64_t W, int num_levels,

@@ -5,8 +5,9 @@ The reference trains through matmul -> / sqrt(D) -> avg_pool2d -> grid_sample
 the lookups' backwards leave), d fmap1 = F2 dV^T and d fmap2 = F1 dV with dV the
 pooling-chain fold of G / sqrt(D).  The check: ``dxr_fmap_grads`` (dV folded
 inside the MFMA operand loads, never stored) against ``dxr_pyramid_backward``
-(dV in HBM, itself pinned by the reference autograd goldens) followed by float64
-GEMMs, and against the same dV through float32 rocBLAS (the round-2 path): the
+(dV in HBM, itself pinned cell by cell against the float64 fold by
+tests/test_gpu_lookup_backward.py::test_pyramid_backward_matches_float64_fold)
+followed by float64 GEMMs, and against the same dV through float32 rocBLAS (the round-2 path): the
 fused GEMMs must be at least as close to float64 as float32 BLAS is (f32 class),
 and within 1e-5 of max|grad|.
 """

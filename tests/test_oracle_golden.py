@@ -255,3 +255,41 @@ def test_oracle_motion_conv1x1(name):
     assert got.shape == d["out"].shape == (d["B"], d["cout"], d["H"], d["W"])
     tolerance_check(got.astype(np.float32), d["out"], 1e-5)
     assert (got == 0).any() and (got > 0).any()   # the ReLU clips part of the output
+
+
+# --------------------------------------------------------------------------- lookup backward
+def _lookup_backward_cases():
+    import test_gpu_lookup_backward as lb
+    return lb.CASE_RADII
+
+
+@pytest.mark.parametrize("cid,r", _lookup_backward_cases(),
+                         ids=[f"{c}-r{r}" for c, r in _lookup_backward_cases()])
+def test_lookup_backward_oracle_is_adjoint_of_lookup(cid, r):
+    """tests/test_gpu_lookup_backward.py checks the kernel cell by cell against
+    oracle.corr_lookup_backward at inputs the backward goldens (``normal``
+    coordinates, r = 3 and 4) do not cover: every radius, windows off the level,
+    integer, far and non-finite coordinates, row-major and 1 x 1 levels.  There
+    the restatement is pinned to the forward one (itself bit-exact against the
+    reference) by linearity: <corr_lookup(P, c), g> = sum_l <P_l, G_l> for a
+    random float64 pyramid P, NaN outputs (non-finite coordinates, a 1 x 1
+    level) contributing nothing on either side.  Float64 sums of ~1e5 terms:
+    1e-10 of sum |terms|.  Also the cases' non-vacuity, under the oracle alone."""
+    import test_gpu_lookup_backward as lb
+    B, H, W, L, cs, gs = lb.case_inputs(cid, r)
+    shapes = lb.level_shapes(H, W, L)
+    ref, mag = lb.case_reference(cid, r)
+    lb.check_non_vacuous(cid, shapes, mag)
+    P = [dg.normal(77 + lvl, B * H * W * h * w).reshape(B * H * W, h, w)
+         for lvl, (h, w) in enumerate(shapes)]
+    lhs = terms = 0.0
+    for c, g in zip(cs, gs):
+        out = oracle.corr_lookup(P, c, r)
+        assert out.dtype == np.float64
+        lhs += float(np.nansum(out * g))
+        terms += float(np.nansum(np.abs(out * g)))
+    rhs = float(sum((p * q).sum() for p, q in zip(P, ref)))
+    terms = min(terms, float(sum(np.abs(p * q).sum() for p, q in zip(P, ref))))
+    assert all(np.isfinite(q).all() for q in ref)
+    assert (terms > 0) == (cid != "far")
+    assert abs(lhs - rhs) <= 1e-10 * terms, (lhs, rhs, terms)
