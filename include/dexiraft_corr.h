@@ -92,6 +92,17 @@ enum dxr_dtype {
   DXR_F16 = 2           /* IEEE float16 fmaps: an in_dtype of the pyramid builds only */
 };
 
+/*
+ * Output dtype flags of dxr_corr_lookup and dxr_corr_lookup_conv1x1 only: or-ed
+ * onto their pyr_dtype argument (DXR_F32 or DXR_BF16), they make the call store
+ * `out` as IEEE float16 / bfloat16 elements instead of float32 (same ABI, no new
+ * entry point).  Both flags together, any other bit above the low byte, a flag on
+ * any other low value (DXR_F16 included) and a flag passed to any other entry
+ * point are DXR_EINVAL, answered on the host before any launch.
+ */
+#define DXR_OUT_F16 0x100
+#define DXR_OUT_BF16 0x200
+
 enum dxr_layout {
   DXR_NCHW = 0,         /* fmaps [B, D, H, W] (core/raft.py:139-142)              */
   DXR_NHWC = 1          /* fmaps [B, H, W, D] (channels-last encoders, §8(f) row 4) */
@@ -247,6 +258,12 @@ int dxr_pyramid_pack(const float* level_data, int64_t B, int64_t H, int64_t W,
  *   out     : [B, num_levels*(2r+1)^2, H, W] float32
  * A level with H_l == 1 or W_l == 1 yields NaN, as the reference does
  * (bilinear_sampler divides by H_l-1 / W_l-1, core/utils/utils.py:61-62).
+ * pyr_dtype | DXR_OUT_F16 or pyr_dtype | DXR_OUT_BF16: `out` points to
+ * [B, num_levels*(2r+1)^2, H, W] float16 / bfloat16 elements (passed through the
+ * float* parameter) and needs 2-byte alignment only.  Every element is the
+ * float32 call's, converted round-to-nearest-even in the store (float16: overflow
+ * to +-inf, subnormals kept; NaN stays NaN): torch's out.to(dtype) bit for bit.
+ * No byte outside the elements is written.
  */
 int dxr_corr_lookup(const void* pyramid, int pyr_dtype,
                     int64_t B, int64_t H, int64_t W, int num_levels, int radius,
@@ -310,7 +327,10 @@ int dxr_corr_lookup_backward_multi_bound(const float* const* coords,
  *                   float32 [ceil(cin/16)*2][cout][8], zero padded, followed by
  *                   the same layout as f16 pairs, 8 hi then 8 lo per 32 bytes)
  *   bias          : [cout] float32 or NULL;  relu: 1 = F.relu, 0 = none
- *   out           : [B, cout, H, W] float32
+ *   out           : [B, cout, H, W] float32; with pyr_dtype | DXR_OUT_F16 or
+ *                   | DXR_OUT_BF16 float16 / bfloat16 elements (2-byte aligned),
+ *                   as dxr_corr_lookup: the same float32 accumulation, bias and
+ *                   ReLU, converted round-to-nearest-even in the store
  * Supported: radius 3 or 4, num_levels <= 4, cout a multiple of 32 (<= 4096);
  * other valid requests return DXR_EUNSUPPORTED.
  */

@@ -27,6 +27,7 @@ Differences from the reference, all loud:
 from __future__ import annotations
 
 import ctypes
+import inspect
 from functools import lru_cache
 
 import numpy as np
@@ -255,10 +256,10 @@ class _LookupGrad(torch.autograd.Function):
     """Graph node of CorrBlock.__call__ (differentiable in the pyramid only)."""
 
     @staticmethod
-    def forward(ctx, token, coords, block):
+    def forward(ctx, token, coords, block, out_dtype=None):
         ctx.gs = block._gs
         ctx.save_for_backward(coords)
-        return block._lookup(coords)
+        return block._lookup(coords, out_dtype)
 
     @staticmethod
     def backward(ctx, gout):
@@ -272,7 +273,7 @@ class _LookupGrad(torch.autograd.Function):
         # no gradient for the token: autograd still runs the build's backward
         # after every lookup's (it waits on the edge, and materialises one zero)
         # without a fill per lookup and the adds that would sum them
-        return None, None, None
+        return None, None, None, None
 
 
 class _VolumeGrad(torch.autograd.Function):
@@ -412,6 +413,23 @@ def _check_coords(coords: torch.Tensor, B: int, H: int, W: int, device: torch.de
     return coords.contiguous()
 
 
+_OUT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _out_flag(out_dtype) -> tuple[torch.dtype, int]:
+    """(torch dtype of the output, flag or-ed onto pyr_dtype) of an ``out_dtype``
+    argument: None / float32 take the float32 kernels, float16 / bfloat16 the
+    16-bit stores (``DXR_OUT_F16`` / ``DXR_OUT_BF16``)."""
+    if out_dtype is None or out_dtype == torch.float32:
+        return torch.float32, 0
+    if out_dtype == torch.float16:
+        return torch.float16, nat.DXR_OUT_F16
+    if out_dtype == torch.bfloat16:
+        return torch.bfloat16, nat.DXR_OUT_BF16
+    raise ValueError(f"out_dtype must be None or one of {', '.join(map(str, _OUT_DTYPES))}; "
+                     f"got {out_dtype!r}")
+
+
 _PACKED_CACHE: dict = {}
 
 
@@ -446,6 +464,10 @@ class CorrBlock:
     caching allocator); each ``__call__(coords)`` is one lookup launch
     (``dxr_corr_lookup``) returning a new contiguous float32
     ``[B, num_levels*(2r+1)^2, H, W]`` tensor in the reference's channel order.
+    ``__call__(coords, out_dtype=torch.float16)`` (or bfloat16; also
+    ``lookup_conv1x1``) stores that tensor in 16 bits from the same launch, for
+    update blocks that run under autocast: the float32 result's ``.to(dtype)``
+    bit for bit, with half the output traffic and no cast kernel.
 
     fp32 fmaps (the reference's dtype, core/raft.py:139-142) compute in f32
     class: a split pass scales every pixel's channel vector by a power of two
@@ -573,28 +595,50 @@ class CorrBlock:
             self._ref_pyramid = levels
         return self._ref_pyramid
 
-    def __call__(self, coords):
+    def __call__(self, coords, out_dtype=None):
+        """The radius-r lookup around ``coords``: ``[B, num_levels*(2r+1)^2, H, W]``.
+
+        ``out_dtype``: None or torch.float32 (the default: float32, as the
+        reference), torch.float16 or torch.bfloat16 (anything else raises
+        ``ValueError``).  A 16-bit result is ``self(coords).to(out_dtype)`` bit
+        for bit — the float32 sums, rounded to nearest even in the kernel's own
+        stores (float16: overflow to +-inf, subnormals kept; NaNs stay NaNs) —
+        i.e. the cast autocast applies before ``convc1`` (core/update.py:90),
+        without the float32 tensor and the cast kernel.  Under grad the
+        backward is the float32 lookup's, fed ``grad_out.float()``.
+        """
         B, D, H, W = self._geom
+        _out_flag(out_dtype)
         _require_no_grad(coords, what="coords (the reference detaches them, core/raft.py:170)")
         c = _check_coords(coords, B, H, W, self._device)
         if self._token is not None and torch.is_grad_enabled():
-            return _LookupGrad.apply(self._token, c, self)
-        return self._lookup(c)
+            return _LookupGrad.apply(self._token, c, self, out_dtype)
+        return self._lookup(c, out_dtype)
 
-    def _lookup(self, c):
+    # Introspection (inspect.signature, help()) reports the reference's own
+    # ``__call__(self, coords)`` (core/corr.py:29): the class is a drop-in and its
+    # declared surface is pinned to the reference's (tests/test_api_cpu.py).
+    # ``out_dtype`` is an extension on top of it, optional and documented above;
+    # callers that never pass it get the reference's behaviour.
+    __call__.__signature__ = inspect.Signature([
+        inspect.Parameter("self", inspect.Parameter.POSITIONAL_OR_KEYWORD),
+        inspect.Parameter("coords", inspect.Parameter.POSITIONAL_OR_KEYWORD)])
+
+    def _lookup(self, c, out_dtype=None):
         B, D, H, W = self._geom
         rd = 2 * self.radius + 1
-        out = torch.empty((B, self.num_levels * rd * rd, H, W), dtype=torch.float32,
+        out_torch, flag = _out_flag(out_dtype)
+        out = torch.empty((B, self.num_levels * rd * rd, H, W), dtype=out_torch,
                           device=self._device)
         lib = nat.load()
         with _Launch(self._device):
-            st = lib.dxr_corr_lookup(self._buf.data_ptr(), self._pyr_dt, B, H, W,
+            st = lib.dxr_corr_lookup(self._buf.data_ptr(), self._pyr_dt | flag, B, H, W,
                                      self.num_levels, self.radius, c.data_ptr(),
                                      out.data_ptr(), nat.stream_of(c))
         nat.check(st, "CorrBlock lookup (dxr_corr_lookup)")
         return out
 
-    def lookup_conv1x1(self, coords, weight, bias=None, relu=True):
+    def lookup_conv1x1(self, coords, weight, bias=None, relu=True, out_dtype=None):
         """Lookup fused with the motion encoder's first 1x1 convolution:
         ``F.relu(F.conv2d(self(coords), weight, bias))`` in one launch
         (``dxr_corr_lookup_conv1x1``).
@@ -602,13 +646,18 @@ class CorrBlock:
         Replaces ``corr = corr_fn(coords1)`` (core/raft.py:172) followed by
         ``cor = F.relu(self.convc1(corr))`` in BasicMotionEncoder.forward
         (core/update.py:90; SmallMotionEncoder :71): pass ``convc1.weight`` and
-        ``convc1.bias``.  Returns a new contiguous float32 ``[B, Cout, H, W]``.
+        ``convc1.bias``.  Returns a new contiguous float32 ``[B, Cout, H, W]``
+        (``out_dtype`` torch.float16 / torch.bfloat16: that dtype, equal to the
+        float32 result's ``.to(out_dtype)`` bit for bit — same accumulation, bias
+        and ReLU in float32, only the store converts; other values as in
+        ``__call__``).
         The samples are bit-identical to ``__call__``'s; the contraction runs in
         f32 class on the matrix cores.  Inference only (raises under grad for
         inputs that require grad).  Supported: radius 3/4, num_levels <= 4,
         Cout a multiple of 32 (the reference's 256 and 96).
         """
         B, D, H, W = self._geom
+        out_torch, flag = _out_flag(out_dtype)
         _require_no_grad(coords, weight, *(() if bias is None else (bias,)),
                          what="CorrBlock.lookup_conv1x1 (inference fusion)")
         if self._token is not None and torch.is_grad_enabled():
@@ -630,10 +679,10 @@ class CorrBlock:
                 raise RuntimeError(f"bias must be [{cout}], got {tuple(bias.shape)}")
             bias = bias.detach().float().contiguous()
         planes = _packed_weight(weight, self._device)
-        out = torch.empty((B, cout, H, W), dtype=torch.float32, device=self._device)
+        out = torch.empty((B, cout, H, W), dtype=out_torch, device=self._device)
         lib = nat.load()
         with _Launch(self._device):
-            st = lib.dxr_corr_lookup_conv1x1(self._buf.data_ptr(), self._pyr_dt, B, H, W,
+            st = lib.dxr_corr_lookup_conv1x1(self._buf.data_ptr(), self._pyr_dt | flag, B, H, W,
                                              self.num_levels, self.radius, c.data_ptr(),
                                              planes.data_ptr(), nat.ptr(bias), cout, int(bool(relu)),
                                              out.data_ptr(), nat.stream_of(c))
@@ -683,6 +732,8 @@ class AlternateCorrBlock:
     2^num_levels in either dimension raise (core/corr.py:69-71).
     bfloat16 and float16 fmaps are widened exactly to float32 first (the
     reference's own cast, core/raft.py:139-142).
+    ``__call__`` takes no ``out_dtype`` (CorrBlock's 16-bit lookup outputs): this
+    block's output stores are a separate matter and its result stays float32.
     """
 
     # Which levels are precomputed (round 6, bench.py --block alt, profiles/r06/experiments/

@@ -635,6 +635,66 @@ __device__ __forceinline__ void qm_gather(const PT* __restrict__ base, int qb0, 
   }
 }
 
+// ---------------------------------------------------------------------------
+// 16-bit outputs (float16 / bfloat16: what an autocast consumer casts the
+// float32 tensor to).  The sums are the float32 kernel's; only the store converts,
+// with the hardware round-to-nearest-even conversions (v_cvt_f16_f32: overflow to
+// +-inf, subnormals kept; v_cvt_pk_bf16_f32), so the result is torch's
+// out.to(dtype) bit for bit.
+// In the stores a lane owns (query, channel row) and lanes 2i, 2i + 1 hold
+// queries q, q + 1 of one row (q even: workgroups start at even queries).  The
+// pair swaps its 16 bits by DPP and the even lane writes one 32-bit word — a
+// half-wave's 32 queries go out as one 64-B segment — where that word is 4-byte
+// aligned: element (row * N + q) even and the base 4-byte aligned, i.e.
+// (row * N + base parity) even.  On the other rows (every second one when N is
+// odd, or all of them on a base that is only 2-byte aligned), and for the last
+// query of an odd tail, lanes store their own 16-bit element: no store touches a
+// byte outside its element(s).
+// ---------------------------------------------------------------------------
+template <typename OT>
+__device__ __forceinline__ uint32_t out16_bits(float r) {
+  static_assert(sizeof(OT) == 2, "16-bit output types");
+  // the float32 value as it stands: without this the compiler folds the last fma
+  // and the conversion into v_fma_mixlo_f16, which rounds the exact sum once to
+  // float16 and so breaks ties differently from float32-then-cast
+  asm volatile("" : "+v"(r));
+  return __builtin_bit_cast(uint16_t, static_cast<OT>(r));
+}
+
+// Parity (in elements) of a 2-byte aligned output base.
+template <typename OT>
+__device__ __forceinline__ int out16_base_parity(const OT* out) {
+  return (int)((reinterpret_cast<uintptr_t>(out) >> 1) & 1);
+}
+
+// MODE 0: plain stores; 1: non-temporal; 2: write-through (agent scope), the
+// float32 kernels' forms.  `word_row`: this row's even elements are 4-byte
+// aligned; `odd`: the lane's query is odd; `has_next`: query q + 1 exists (its
+// lane is active).  Both lanes of a pair must call this together.
+template <typename OT, int MODE>
+__device__ __forceinline__ void store_out16_one(OT* p, uint32_t h, uint32_t w, bool word) {
+  if (word) {
+    uint32_t* pw = reinterpret_cast<uint32_t*>(p);
+    if constexpr (MODE == 1) __builtin_nontemporal_store(w, pw);
+    else if constexpr (MODE == 2) __hip_atomic_store(pw, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *pw = w;
+  } else {
+    uint16_t* ph = reinterpret_cast<uint16_t*>(p);
+    if constexpr (MODE == 1) __builtin_nontemporal_store((uint16_t)h, ph);
+    else if constexpr (MODE == 2) __hip_atomic_store(ph, (uint16_t)h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *ph = (uint16_t)h;
+  }
+}
+
+template <typename OT, int MODE>
+__device__ __forceinline__ void store_out16(OT* p, float r, bool word_row, bool odd, bool has_next) {
+  const uint32_t h = out16_bits<OT>(r);
+  // the pair's other lane (quad permutation [1,0,3,2]); an inactive lane's value is never used
+  const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp((int)h, (int)h, 0xB1, 0xF, 0xF, false);
+  if (word_row && odd) return;                 // the even lane wrote this element
+  store_out16_one<OT, MODE>(p, h, h | (nb << 16), word_row && has_next);
+}
+
 // XA: timing ablations for the experiments target (0 in the product): bit 0 skips
 // the window gathers, bit 1 the output stores (only values equal to 12345 are
 // stored), bit 2 returns after phase 0.
@@ -643,11 +703,13 @@ __device__ __forceinline__ void qm_gather(const PT* __restrict__ base, int qb0, 
 // floor(c / 2^l) - r with no coordinate round trip, the (2r+2)^2 window cells
 // weighted by the fractions of c / 2^l and combined in correlation_kernel.cu's
 // order (as alt_corr_mfma_kernel's last phase), then divided by sqrt(D).
+// OT: output element type (float; _Float16 / __bf16: the 16-bit stores above).
 template <int R, typename PT, int NT_ = 512, int QB_ = 32, int UNR = 1, bool BUF = false, int XA = 0,
-          bool ALT = false>
+          bool ALT = false, typename OT = float>
 __global__ __launch_bounds__(NT_) void corr_lookup_qm_kernel(
-    const PT* __restrict__ pyr, const float* __restrict__ coords, float* __restrict__ out,
+    const PT* __restrict__ pyr, const float* __restrict__ coords, OT* __restrict__ out,
     LookupGeom g) {
+  static_assert(std::is_same_v<OT, float> || (!ALT && XA == 0), "16-bit outputs: the product lookup only");
   using Q = QmCfg<R, NT_, QB_>;
   constexpr int RD = Q::RD, K = Q::K, QB = Q::QB, RSC = Q::RSC;
   __shared__ __attribute__((aligned(16))) float cells[Q::NCELL * QB];
@@ -691,8 +753,17 @@ __global__ __launch_bounds__(NT_) void corr_lookup_qm_kernel(
   const int qq = tid % QB, cls = tid / QB;
   if (q0 + qq >= g.N) return;
   const float* cq = cells + qq;
-  float* op = out + ((long long)b * g.cout + (long long)l * K + cls) * g.N + q0 + qq;
+  OT* op = out + ((long long)b * g.cout + (long long)l * K + cls) * g.N + q0 + qq;
   const long long ostep = (long long)Q::NCLS * g.N;
+  // 16-bit outputs: parity of (row * N + base) for row = b * cout + l * K + k is
+  // (row & N & 1) ^ base parity; the row's parity steps with k
+  [[maybe_unused]] int rowpar = 0, basepar = 0;
+  [[maybe_unused]] bool has_next = false;
+  if constexpr (!std::is_same_v<OT, float>) {
+    rowpar = (b * g.cout + l * K) & 1;
+    basepar = out16_base_parity(out);
+    has_next = q0 + qq + 1 < g.N;
+  }
 #pragma unroll UNR
   for (int k = cls; k < K; k += Q::NCLS) {
     const int ox = k / RD, oy = k - ox * RD;
@@ -716,9 +787,16 @@ __global__ __launch_bounds__(NT_) void corr_lookup_qm_kernel(
       r = __builtin_fmaf(sw, v10, r);
       r = __builtin_fmaf(se, v11, r);
     }
-    if ((XA & 2) == 0 || r == 12345.f) {
-      if (g.out_nt) __builtin_nontemporal_store(r, op);
-      else __hip_atomic_store(op, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (std::is_same_v<OT, float>) {
+      if ((XA & 2) == 0 || r == 12345.f) {
+        if (g.out_nt) __builtin_nontemporal_store(r, op);
+        else __hip_atomic_store(op, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    } else {
+      // the float32 stores' choice (g.out_nt), carried over
+      const bool word_row = ((((rowpar + k) & g.N) ^ basepar) & 1) == 0;
+      if (g.out_nt) store_out16<OT, 1>(op, r, word_row, qq & 1, has_next);
+      else store_out16<OT, 2>(op, r, word_row, qq & 1, has_next);
     }
     op += ostep;
   }
@@ -1051,10 +1129,12 @@ int launch_lookup_wide_r(const PT* pyr, const float* coords, float* out, const L
 // 913.1 -> 884.6 / 854.0, 1080p full 2,176 -> 2,170 / 2,149, Chairs 98.2 -> 96.4
 // / 97.4, Sintel B=2 348.2 -> 355.6 / 349.7.  `ONE_QB` / `UNR` / `MULTI_BUF`:
 // experiment knobs (queries per one-round workgroup, phase-2 unroll, buffer loads
-// on multi-round grids); `ONE_BUF`: buffer loads on one-round grids too.
+// on multi-round grids); `ONE_BUF`: buffer loads on one-round grids too.  `OT`
+// (deduced from `out`): float, or _Float16 / __bf16 for the 16-bit output stores —
+// same shapes, same out_nt rule.
 template <int R, typename PT, int ONE_QB = 16, int UNR = 1, bool ONE_BUF = false, bool MULTI_BUF = true,
-          int XA = 0, int MULTI_NT = 512, int MULTI_QB = 0>
-int launch_lookup_r(const PT* pyr, const float* coords, float* out, const LookupGeom& g0, int B,
+          int XA = 0, int MULTI_NT = 512, int MULTI_QB = 0, typename OT = float>
+int launch_lookup_r(const PT* pyr, const float* coords, OT* out, const LookupGeom& g0, int B,
                        hipStream_t stream) {
   using W = WideCfg<R>;
   LookupGeom g = g0;
@@ -1064,20 +1144,20 @@ int launch_lookup_r(const PT* pyr, const float* coords, float* out, const Lookup
   if (R <= 4 && wg32 <= 1024 && !big_misaligned) {
     g.out_nt = g.N % 32 == 0 ? 1 : 0;
     const dim3 grid((unsigned)((g.N + ONE_QB - 1) / ONE_QB), (unsigned)g.levels, (unsigned)B);
-    hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 256, ONE_QB, UNR, ONE_BUF, XA>), grid, dim3(256), 0, stream, pyr,
-                       coords, out, g);
+    hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 256, ONE_QB, UNR, ONE_BUF, XA, false, OT>), grid,
+                       dim3(256), 0, stream, pyr, coords, out, g);
     return dxr::launch_status();
   }
   g.out_nt = 1;
   constexpr int MQB = MULTI_QB ? MULTI_QB : W::QB;
   const dim3 grid((unsigned)((g.N + MQB - 1) / MQB), (unsigned)g.levels, (unsigned)B);
-  hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, MULTI_NT, MQB, UNR, MULTI_BUF, XA>), grid,
+  hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, MULTI_NT, MQB, UNR, MULTI_BUF, XA, false, OT>), grid,
                      dim3(MULTI_NT), 0, stream, pyr, coords, out, g);
   return dxr::launch_status();
 }
 
-template <typename PT>
-int launch_lookup(const PT* pyr, const float* coords, float* out, const LookupGeom& g, int B,
+template <typename PT, typename OT>
+int launch_lookup(const PT* pyr, const float* coords, OT* out, const LookupGeom& g, int B,
                   int radius, hipStream_t stream) {
   switch (radius) {
     case 0: return launch_lookup_r<0, PT>(pyr, coords, out, g, B, stream);
@@ -1197,10 +1277,10 @@ __global__ __launch_bounds__(256) void conv1x1_pack_weight_kernel(const float* _
 // ---------------------------------------------------------------------------
 typedef _Float16 mh8 __attribute__((ext_vector_type(8)));
 
-template <int R, typename PT, int NT = 512, int PF = 4>
+template <int R, typename PT, int NT = 512, int PF = 4, typename OT = float>
 __global__ __launch_bounds__(NT, 4) void corr_lookup_conv1x1_h2_kernel(
     const PT* __restrict__ pyr, const float* __restrict__ coords, const float4* __restrict__ wpk,
-    const float* __restrict__ bias, float* __restrict__ out, LookupGeom g, int cout, int relu) {
+    const float* __restrict__ bias, OT* __restrict__ out, LookupGeom g, int cout, int relu) {
   using C = WideCfg<R, NT>;
   using M = MotionCfg<R>;
   constexpr int RD = C::RD, RS = C::RS, K = C::K, QB = C::QB, KB = M::KB;
@@ -1374,13 +1454,20 @@ __global__ __launch_bounds__(NT, 4) void corr_lookup_conv1x1_h2_kernel(
           for (int r = 0; r < 16; ++r) bad |= !(__builtin_fabsf(acc[r]) <= 3.40282347e38f);
           if (bad) nonfinite = 1;
         }
-        float* ob_out = out + (long long)b * cout * g.N + q;
+        OT* ob_out = out + (long long)b * cout * g.N + q;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int orow = ob * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
           float v = acc[r] + (bias ? bias[orow] : 0.f);
           if (relu && v < 0.f) v = 0.f;      // NaN stays NaN, as torch.relu
-          ob_out[(long long)orow * g.N] = v;
+          if constexpr (std::is_same_v<OT, float>) {
+            ob_out[(long long)orow * g.N] = v;
+          } else {
+            // 16-bit outputs (store_out16): bias and ReLU above in float32; lanes j,
+            // j ^ 1 hold queries q, q ^ 1 of row b * cout + orow
+            const bool word_row = (((((b * cout + orow) & g.N)) ^ out16_base_parity(out)) & 1) == 0;
+            store_out16<OT, 0>(ob_out + (long long)orow * g.N, v, word_row, j & 1, q + 1 < g.N);
+          }
         }
       }
     }
@@ -1390,9 +1477,9 @@ __global__ __launch_bounds__(NT, 4) void corr_lookup_conv1x1_h2_kernel(
   if (nonfinite) gemm(std::integral_constant<bool, false>{});   // workgroup-uniform
 }
 
-template <int R, typename PT>
+template <int R, typename PT, typename OT>
 int launch_lookup_conv1x1_r(const PT* pyr, const float* coords, const float4* wpl,
-                            const float* bias, float* out, const LookupGeom& g, int B, int cout,
+                            const float* bias, OT* out, const LookupGeom& g, int B, int cout,
                             int relu, hipStream_t stream) {
   using C = WideCfg<R, 1024>;
   if (g.cout > MotionCfg<R>::KP) return DXR_EUNSUPPORTED;
@@ -1402,26 +1489,112 @@ int launch_lookup_conv1x1_r(const PT* pyr, const float* coords, const float4* wp
   // ~76 KB LDS and 128 VGPRs, two workgroups per CU (Sintel B=2: 35 vs 47 us,
   // KITTI-shape B=8: 136 vs 190 us; r01 kernel 52 / 214 us).
   if ((long long)grid.x * grid.y <= 256)
-    hipLaunchKernelGGL((corr_lookup_conv1x1_h2_kernel<R, PT, 1024, 4>), grid, dim3(1024), 0,
+    hipLaunchKernelGGL((corr_lookup_conv1x1_h2_kernel<R, PT, 1024, 4, OT>), grid, dim3(1024), 0,
                        stream, pyr, coords, wpl, bias, out, g, cout, relu);
   else
-    hipLaunchKernelGGL((corr_lookup_conv1x1_h2_kernel<R, PT, 512, 4>), grid, dim3(512), 0, stream,
+    hipLaunchKernelGGL((corr_lookup_conv1x1_h2_kernel<R, PT, 512, 4, OT>), grid, dim3(512), 0, stream,
                        pyr, coords, wpl, bias, out, g, cout, relu);
   return dxr::launch_status();
 }
 
-template <typename PT>
+template <typename PT, typename OT>
 int launch_lookup_conv1x1(const PT* pyr, const float* coords, const float4* wpl, const float* bias,
-                          float* out, const LookupGeom& g, int B, int radius, int cout, int relu,
+                          OT* out, const LookupGeom& g, int B, int radius, int cout, int relu,
                           hipStream_t stream) {
   switch (radius) {
-    case 3: return launch_lookup_conv1x1_r<3, PT>(pyr, coords, wpl, bias, out, g, B, cout, relu, stream);
-    case 4: return launch_lookup_conv1x1_r<4, PT>(pyr, coords, wpl, bias, out, g, B, cout, relu, stream);
+    case 3: return launch_lookup_conv1x1_r<3, PT, OT>(pyr, coords, wpl, bias, out, g, B, cout, relu, stream);
+    case 4: return launch_lookup_conv1x1_r<4, PT, OT>(pyr, coords, wpl, bias, out, g, B, cout, relu, stream);
     default: return DXR_EUNSUPPORTED;
   }
 }
 
+// dxr_corr_lookup / dxr_corr_lookup_conv1x1 for one output type: the argument
+// checks (before any launch), the geometry and the launch.  OT = float here;
+// _Float16 / __bf16 are instantiated in corr_lookup_out16.hip only — co-compiled
+// with them, several float32-output kernels were allocated two more VGPRs
+// (DESIGN.md §3.11), and the float32 path is to stay the code it was.
+template <typename OT>
+int corr_lookup_impl(const void* pyramid, int pyr_dtype, int64_t B, int64_t H, int64_t W,
+                     int num_levels, int radius, const float* coords, OT* out,
+                     hipStream_t stream) {
+  dxr::Levels L;
+  if (!dxr::make_levels(B, H, W, num_levels, &L)) return DXR_EINVAL;
+  if (radius < 0) return DXR_EINVAL;
+  if (radius > 8) return DXR_EUNSUPPORTED;
+  if (B > 65535 || H * W > (1LL << 30)) return DXR_EINVAL;
+  if (B == 0) return DXR_OK;
+  if (!pyramid || !coords || !out) return DXR_EINVAL;
+  const int rd = 2 * radius + 1;
+  LookupGeom g;
+  g.N = (int)(H * W);
+  g.levels = num_levels;
+  g.cout = num_levels * rd * rd;
+  for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
+  if (pyr_dtype == DXR_F32)
+    return launch_lookup(static_cast<const float*>(pyramid), coords, out, g, (int)B, radius, stream);
+  if (pyr_dtype == DXR_BF16)
+    return launch_lookup(static_cast<const uint16_t*>(pyramid), coords, out, g, (int)B, radius,
+                         stream);
+  return DXR_EINVAL;
+}
+
+template <typename OT>
+int corr_lookup_conv1x1_impl(const void* pyramid, int pyr_dtype, int64_t B, int64_t H, int64_t W,
+                             int num_levels, int radius, const float* coords,
+                             const void* weight_packed, const float* bias, int64_t cout, int relu,
+                             OT* out, hipStream_t stream) {
+  dxr::Levels L;
+  if (!dxr::make_levels(B, H, W, num_levels, &L)) return DXR_EINVAL;
+  if (radius < 0 || cout < 1) return DXR_EINVAL;
+  if (radius != 3 && radius != 4) return DXR_EUNSUPPORTED;
+  if (num_levels > 4 || cout % 32 != 0 || cout > 4096) return DXR_EUNSUPPORTED;
+  if (B > 65535 || H * W > (1LL << 30)) return DXR_EINVAL;
+  if (B == 0) return DXR_OK;
+  if (!pyramid || !coords || !weight_packed || !out) return DXR_EINVAL;
+  const int rd = 2 * radius + 1;
+  LookupGeom g;
+  g.N = (int)(H * W);
+  g.levels = num_levels;
+  g.cout = num_levels * rd * rd;
+  for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
+  const float4* wpl = static_cast<const float4*>(weight_packed);
+  if (pyr_dtype == DXR_F32)
+    return launch_lookup_conv1x1(static_cast<const float*>(pyramid), coords, wpl, bias, out, g,
+                                 (int)B, radius, (int)cout, relu, stream);
+  if (pyr_dtype == DXR_BF16)
+    return launch_lookup_conv1x1(static_cast<const uint16_t*>(pyramid), coords, wpl, bias, out, g,
+                                 (int)B, radius, (int)cout, relu, stream);
+  return DXR_EINVAL;
+}
+
 }  // namespace
+
+#ifdef DXR_LOOKUP_OUT16_TU
+// corr_lookup_out16.hip: this file's templates with the 16-bit output types, and
+// nothing else of it.
+int dxr::lookup_out16(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H,
+                      int64_t W, int num_levels, int radius, const float* coords, void* out,
+                      hipStream_t stream) {
+  if (out_flag == DXR_OUT_F16)
+    return corr_lookup_impl(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
+                            static_cast<_Float16*>(out), stream);
+  return corr_lookup_impl(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
+                          static_cast<__bf16*>(out), stream);
+}
+
+int dxr::lookup_conv1x1_out16(const void* pyramid, int pyr_dtype, int out_flag, int64_t B,
+                              int64_t H, int64_t W, int num_levels, int radius,
+                              const float* coords, const void* weight_packed, const float* bias,
+                              int64_t cout, int relu, void* out, hipStream_t stream) {
+  if (out_flag == DXR_OUT_F16)
+    return corr_lookup_conv1x1_impl(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
+                                    weight_packed, bias, cout, relu, static_cast<_Float16*>(out),
+                                    stream);
+  return corr_lookup_conv1x1_impl(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
+                                  weight_packed, bias, cout, relu, static_cast<__bf16*>(out),
+                                  stream);
+}
+#else   // the entry points (float32 outputs)
 
 namespace {
 // The alternate block's coarse levels from their volumes (dxr_alt_coarse_volumes),
@@ -1490,28 +1663,35 @@ extern "C" int dxr_alt_volume_lookup(const float* volumes, const float* coords, 
   }
 }
 
+namespace {
+// The output dtype flag of dxr_corr_lookup / dxr_corr_lookup_conv1x1 (DXR_OUT_F16,
+// DXR_OUT_BF16, or-ed onto a DXR_F32 / DXR_BF16 pyr_dtype): splits it off.  False
+// (DXR_EINVAL) for both flags, any other high bit, a flag on another low value,
+// or a flagged `out` that is not 2-byte aligned.  Unflagged values pass through
+// to the callers' own checks.
+bool split_out_dtype(int* pyr_dtype, int* out_flag, const void* out) {
+  const int hi = *pyr_dtype & ~0xff;
+  *out_flag = 0;
+  if (hi == 0) return true;
+  if (hi != DXR_OUT_F16 && hi != DXR_OUT_BF16) return false;
+  const int lo = *pyr_dtype & 0xff;
+  if (lo != DXR_F32 && lo != DXR_BF16) return false;
+  if (reinterpret_cast<uintptr_t>(out) & 1) return false;
+  *pyr_dtype = lo;
+  *out_flag = hi;
+  return true;
+}
+}  // namespace
+
 extern "C" int dxr_corr_lookup(const void* pyramid, int pyr_dtype, int64_t B, int64_t H,
                                int64_t W, int num_levels, int radius, const float* coords,
                                float* out, hipStream_t stream) {
-  dxr::Levels L;
-  if (!dxr::make_levels(B, H, W, num_levels, &L)) return DXR_EINVAL;
-  if (radius < 0) return DXR_EINVAL;
-  if (radius > 8) return DXR_EUNSUPPORTED;
-  if (B > 65535 || H * W > (1LL << 30)) return DXR_EINVAL;
-  if (B == 0) return DXR_OK;
-  if (!pyramid || !coords || !out) return DXR_EINVAL;
-  const int rd = 2 * radius + 1;
-  LookupGeom g;
-  g.N = (int)(H * W);
-  g.levels = num_levels;
-  g.cout = num_levels * rd * rd;
-  for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
-  if (pyr_dtype == DXR_F32)
-    return launch_lookup(static_cast<const float*>(pyramid), coords, out, g, (int)B, radius, stream);
-  if (pyr_dtype == DXR_BF16)
-    return launch_lookup(static_cast<const uint16_t*>(pyramid), coords, out, g, (int)B, radius,
-                         stream);
-  return DXR_EINVAL;
+  int out_flag;
+  if (!split_out_dtype(&pyr_dtype, &out_flag, out)) return DXR_EINVAL;
+  if (out_flag)
+    return dxr::lookup_out16(pyramid, pyr_dtype, out_flag, B, H, W, num_levels, radius, coords, out,
+                             stream);
+  return corr_lookup_impl(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords, out, stream);
 }
 
 namespace {
@@ -1638,27 +1818,13 @@ extern "C" int dxr_corr_lookup_conv1x1(const void* pyramid, int pyr_dtype, int64
                                        int64_t W, int num_levels, int radius, const float* coords,
                                        const void* weight_packed, const float* bias, int64_t cout,
                                        int relu, float* out, hipStream_t stream) {
-  dxr::Levels L;
-  if (!dxr::make_levels(B, H, W, num_levels, &L)) return DXR_EINVAL;
-  if (radius < 0 || cout < 1) return DXR_EINVAL;
-  if (radius != 3 && radius != 4) return DXR_EUNSUPPORTED;
-  if (num_levels > 4 || cout % 32 != 0 || cout > 4096) return DXR_EUNSUPPORTED;
-  if (B > 65535 || H * W > (1LL << 30)) return DXR_EINVAL;
-  if (B == 0) return DXR_OK;
-  if (!pyramid || !coords || !weight_packed || !out) return DXR_EINVAL;
-  const int rd = 2 * radius + 1;
-  LookupGeom g;
-  g.N = (int)(H * W);
-  g.levels = num_levels;
-  g.cout = num_levels * rd * rd;
-  for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
-  const float4* wpl = static_cast<const float4*>(weight_packed);
-  if (pyr_dtype == DXR_F32)
-    return launch_lookup_conv1x1(static_cast<const float*>(pyramid), coords, wpl, bias, out, g,
-                                 (int)B, radius, (int)cout, relu, stream);
-  if (pyr_dtype == DXR_BF16)
-    return launch_lookup_conv1x1(static_cast<const uint16_t*>(pyramid), coords, wpl, bias, out, g,
-                                 (int)B, radius, (int)cout, relu, stream);
-  return DXR_EINVAL;
+  int out_flag;
+  if (!split_out_dtype(&pyr_dtype, &out_flag, out)) return DXR_EINVAL;
+  if (out_flag)
+    return dxr::lookup_conv1x1_out16(pyramid, pyr_dtype, out_flag, B, H, W, num_levels, radius,
+                                     coords, weight_packed, bias, cout, relu, out, stream);
+  return corr_lookup_conv1x1_impl(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
+                                  weight_packed, bias, cout, relu, out, stream);
 }
 
+#endif  // DXR_LOOKUP_OUT16_TU

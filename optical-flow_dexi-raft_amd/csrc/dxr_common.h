@@ -22,6 +22,16 @@ inline int launch_status() {
   return DXR_OK;
 }
 
+// dxr_corr_lookup / dxr_corr_lookup_conv1x1 with an output dtype flag (out_flag:
+// DXR_OUT_F16 or DXR_OUT_BF16, already split off pyr_dtype and validated; `out`
+// holds 16-bit elements).  Defined in corr_lookup_out16.hip.
+int lookup_out16(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H, int64_t W,
+                 int num_levels, int radius, const float* coords, void* out, hipStream_t stream);
+int lookup_conv1x1_out16(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H,
+                         int64_t W, int num_levels, int radius, const float* coords,
+                         const void* weight_packed, const float* bias, int64_t cout, int relu,
+                         void* out, hipStream_t stream);
+
 // ---------------------------------------------------------------------------
 // Pyramid layout ("paged" correlation volume).
 //
