@@ -89,16 +89,29 @@ enum dxr_status {
 enum dxr_dtype {
   DXR_F32 = 0,
   DXR_BF16 = 1,         /* storage as IEEE bfloat16 bit patterns (uint16) */
-  DXR_F16 = 2           /* IEEE float16 fmaps: an in_dtype of the pyramid builds only */
+  DXR_F16 = 2,          /* IEEE float16 fmaps: an in_dtype of the pyramid builds only */
+  /*
+   * IEEE float16 pyramid storage: a pyr_dtype only (never an in_dtype), of
+   * dxr_corr_pyramid_build / _build_ws, dxr_pyramid_unpack / _pack,
+   * dxr_corr_lookup and dxr_corr_lookup_conv1x1.  Every stored cell of every
+   * level is the DXR_F32 pyramid's cell for the same fmaps, rounded once to
+   * float16 with round-to-nearest-even (overflow to +-inf, subnormals kept, NaN
+   * stays NaN): torch's .half() of the float32 pyramid, bit for bit.  Pooled
+   * levels are computed from the float32 values of the level above and rounded
+   * once.  Lookups widen the cells on load (exact) and run the float32
+   * arithmetic unchanged.  Every other entry point that takes a dtype rejects it
+   * as it rejects an unknown one.
+   */
+  DXR_PYR_F16 = 4
 };
 
 /*
  * Output dtype flags of dxr_corr_lookup and dxr_corr_lookup_conv1x1 only: or-ed
- * onto their pyr_dtype argument (DXR_F32 or DXR_BF16), they make the call store
- * `out` as IEEE float16 / bfloat16 elements instead of float32 (same ABI, no new
- * entry point).  Both flags together, any other bit above the low byte, a flag on
- * any other low value (DXR_F16 included) and a flag passed to any other entry
- * point are DXR_EINVAL, answered on the host before any launch.
+ * onto their pyr_dtype argument (DXR_F32, DXR_BF16 or DXR_PYR_F16), they make the
+ * call store `out` as IEEE float16 / bfloat16 elements instead of float32 (same
+ * ABI, no new entry point).  Both flags together, any other bit above the low
+ * byte, a flag on any other low value (DXR_F16 included) and a flag passed to any
+ * other entry point are DXR_EINVAL, answered on the host before any launch.
  */
 #define DXR_OUT_F16 0x100
 #define DXR_OUT_BF16 0x200
@@ -164,6 +177,15 @@ int64_t dxr_pyramid_level_offset(int64_t B, int64_t H, int64_t W, int level);
  * and the caller widens the fmaps to f32.  DXR_F16 is no pyr_dtype, and no
  * dtype of any other entry point (dxr_corr_volume: DXR_EUNSUPPORTED;
  * dxr_transpose moves f16 fmaps as DXR_BF16, any 16-bit pattern).
+ * pyr_dtype DXR_PYR_F16 (a float16 pyramid: the DXR_F32 pyramid of the same
+ * request, each cell rounded once to float16, RNE, in the epilogue's own 16-byte
+ * stores) is built by the two LDS-DMA builds only: DXR_F16 fmaps under the
+ * conditions above, and DXR_F32 fmaps with a workspace, DXR_BUILD_AUTO and
+ * D % 16 == 0 (the pre-split build of dxr_corr_pyramid_build_ws).  Every other
+ * valid request for it (DXR_BF16 fmaps, no or a short workspace for f32 / NCHW
+ * f16 fmaps, DXR_BUILD_EXACT_F32, D % 16 != 0, more than 4 levels) returns
+ * DXR_EUNSUPPORTED before any launch; such a pyramid can be made from a DXR_F32
+ * one, level by level, with dxr_pyramid_unpack + dxr_pyramid_pack.
  *
  * Kernels by request (both build entry points; tests/test_gpu_parity.py
  * test_build_kernel_by_request runs each one by name against the oracle):
@@ -183,6 +205,8 @@ int64_t dxr_pyramid_level_offset(int64_t B, int64_t H, int64_t W, int level);
  *                                        (f16 records, f32 pyramid)
  *   f16 NHWC, D % 32 == 0               corr_build_dma_kernel (rows read in place)
  *   f16 otherwise                       none: DXR_EUNSUPPORTED
+ *   DXR_PYR_F16                         the f32 + workspace and the two f16 rows above,
+ *                                        with float16 stores; otherwise DXR_EUNSUPPORTED
  */
 int dxr_corr_pyramid_build(const void* fmap1, const void* fmap2, int in_dtype,
                            int fmap_layout, int64_t B, int64_t D, int64_t H,
@@ -242,7 +266,9 @@ int dxr_corr_volume(const void* fmap1, const void* fmap2, int in_dtype,
 /*
  * Convert one level between the paged pyramid and the reference layout
  * [B*H*W, H_l, W_l] float32 (core/corr.py:22-27).  Padding cells of the paged
- * storage are neither read nor written.
+ * storage are neither read nor written.  pyr_dtype DXR_F32, DXR_BF16 or
+ * DXR_PYR_F16: unpack widens 16-bit cells exactly, pack rounds float32 to the
+ * pyramid's type to nearest even (float16: overflow to +-inf, subnormals kept).
  */
 int dxr_pyramid_unpack(const void* pyramid, int pyr_dtype, int64_t B, int64_t H,
                        int64_t W, int num_levels, int level, float* out,
@@ -258,6 +284,9 @@ int dxr_pyramid_pack(const float* level_data, int64_t B, int64_t H, int64_t W,
  *   out     : [B, num_levels*(2r+1)^2, H, W] float32
  * A level with H_l == 1 or W_l == 1 yields NaN, as the reference does
  * (bilinear_sampler divides by H_l-1 / W_l-1, core/utils/utils.py:61-62).
+ * A DXR_PYR_F16 pyramid's cells are widened to float32 on load (exact), so the
+ * result is the float32 lookup of the widened pyramid bit for bit; a cell that
+ * overflowed to +-inf in the pyramid gives inf / NaN in the outputs that tap it.
  * pyr_dtype | DXR_OUT_F16 or pyr_dtype | DXR_OUT_BF16: `out` points to
  * [B, num_levels*(2r+1)^2, H, W] float16 / bfloat16 elements (passed through the
  * float* parameter) and needs 2-byte alignment only.  Every element is the

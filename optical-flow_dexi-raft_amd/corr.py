@@ -430,6 +430,28 @@ def _out_flag(out_dtype) -> tuple[torch.dtype, int]:
                      f"got {out_dtype!r}")
 
 
+_PYR_FMAP_DTYPES = (torch.float32, torch.float16)
+
+
+def _f16_pyramid(fmap_dtype: torch.dtype, pyramid_dtype) -> bool:
+    """Whether ``CorrBlock(..., pyramid_dtype=...)`` selects the float16 pyramid
+    (``DXR_PYR_F16``) for fmaps of ``fmap_dtype``.  None keeps every input's
+    default; torch.float32 names the default of float32 / float16 fmaps;
+    torch.float16 selects the float16 pyramid for those fmaps.  Anything else, or
+    a value that contradicts the fmap dtype (bfloat16 fmaps build a bfloat16
+    pyramid), raises ``ValueError``."""
+    if pyramid_dtype is None:
+        return False
+    if not isinstance(pyramid_dtype, torch.dtype) or pyramid_dtype not in _PYR_FMAP_DTYPES:
+        raise ValueError("pyramid_dtype must be None, torch.float32 or torch.float16; "
+                         f"got {pyramid_dtype!r}")
+    if fmap_dtype not in _PYR_FMAP_DTYPES:
+        raise ValueError(f"pyramid_dtype={pyramid_dtype} contradicts {fmap_dtype} fmaps (it "
+                         "applies to float32 and float16 fmaps; bfloat16 fmaps build a bfloat16 "
+                         "pyramid)")
+    return pyramid_dtype == torch.float16
+
+
 _PACKED_CACHE: dict = {}
 
 
@@ -488,9 +510,28 @@ class CorrBlock:
     accumulation rounding (f32 class, unlike the bf16 mode).  Shapes that build
     does not cover (D % 32 != 0) are widened here and take the f32 path.
     Inference only: float16 fmaps that require grad raise, as bfloat16 ones do.
+
+    ``pyramid_dtype`` (an extension: the reference constructor has no such
+    argument, and ``inspect.signature`` reports the reference's four) is None by
+    default, which keeps all of the above.  ``pyramid_dtype=torch.float16`` with
+    float16 or float32 fmaps stores the pyramid in float16 (``DXR_PYR_F16``):
+    every cell of every level is the float32 pyramid's cell for the same fmaps
+    rounded once to nearest even — ``level.half()`` of the default block's
+    levels, bit for bit (overflow to +-inf beyond 65504, subnormals kept) — from
+    the same build kernels' own stores; lookups widen the cells on load and run
+    the float32 arithmetic, so their results are the float32 lookup of the
+    widened pyramid, bit for bit.  Half the pyramid memory, half the build's
+    stores and half the bytes a lookup gathers, at 11 significant bits (under
+    autocast the lookup tensor is rounded to float16 before ``convc1`` anyway).
+    Shapes the fused build does not cover (D % 16 != 0) build the float32
+    pyramid into a temporary and convert it level by level.  ``torch.float32``
+    names the default of float32 / float16 fmaps; other values, or one that
+    contradicts the fmap dtype (bfloat16 fmaps), raise ``ValueError``.  Inference
+    only: fmaps that require grad (under grad mode) and more than 4 levels raise
+    ``NotImplementedError`` before any launch.
     """
 
-    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, pyramid_dtype=None):
         self.num_levels = num_levels
         self.radius = radius
         B, D, H, W = _fmap_geometry(fmap1, fmap2)
@@ -511,6 +552,15 @@ class CorrBlock:
             raise RuntimeError(f"fmaps must be float32, bfloat16 or float16, got {fmap1.dtype}")
         if in_dt != nat.DXR_F32:
             _require_no_grad(fmap1, fmap2, what=f"{str(fmap1.dtype)[6:]} fmaps")
+        pyr16 = _f16_pyramid(fmap1.dtype, pyramid_dtype)
+        if pyr16:
+            # a rounded forward with an exact backward is not offered silently
+            _require_no_grad(fmap1, fmap2, what="a float16 pyramid (pyramid_dtype=torch.float16)")
+            if num_levels > 4:
+                raise NotImplementedError(
+                    "dexiraft_amd: a float16 pyramid has at most 4 levels (levels beyond the "
+                    f"fused four are pooled in float32); got num_levels={num_levels}")
+            pyr_dt, pyr_torch = nat.DXR_PYR_F16, torch.float16
         self._geom = (B, D, H, W)
         self._pyr_dt = pyr_dt
         self._device = fmap1.device
@@ -526,6 +576,8 @@ class CorrBlock:
             # f32 path; the memory format is kept
             self._in_dt = nat.DXR_F32
             f1, f2, st = self._launch_build(fmap1.float(), fmap2.float(), grad)
+        if st == nat.DXR_EUNSUPPORTED and pyr16:
+            st = self._build_f16_pyramid_from_f32(fmap1, fmap2)
         nat.check(st, "CorrBlock build (dxr_corr_pyramid_build_ws)")
         self._level_sizes = sizes
         self._ref_pyramid = None
@@ -533,9 +585,39 @@ class CorrBlock:
             self._gs = _GradState(self._geom, num_levels, radius, self._device, numel)
             self._token = _BuildGrad.apply(f1, f2, self._gs)
 
-    def _launch_build(self, fmap1, fmap2, grad=False):
-        """One build launch into this block's pyramid buffer.  Returns the operand
-        tensors the kernel read and the status.
+    def _build_f16_pyramid_from_f32(self, fmap1, fmap2):
+        """The float16 pyramid of a shape the fused float16-store builds do not
+        cover (D % 16 != 0): the float32 pyramid of the widened fmaps, built into
+        a temporary by the default path, then rounded level by level
+        (``dxr_pyramid_unpack`` + ``dxr_pyramid_pack(..., DXR_PYR_F16)``) — by
+        definition the same pyramid.  Pack writes no padding cell, so the buffer
+        is zero-filled first.  Returns the status."""
+        B, D, H, W = self._geom
+        lib = nat.load()
+        self._in_dt = nat.DXR_F32
+        tmp = torch.empty(self._buf.numel(), dtype=torch.float32, device=self._device)
+        _, _, st = self._launch_build(fmap1.float(), fmap2.float(), False, buf=tmp,
+                                      pyr_dt=nat.DXR_F32)
+        if st != nat.DXR_OK:
+            return st
+        self._buf.zero_()
+        with _Launch(self._device):
+            for lvl, (h, w) in enumerate(_level_sizes(H, W, self.num_levels)):
+                t = torch.empty((B * H * W, h, w), dtype=torch.float32, device=self._device)
+                st = lib.dxr_pyramid_unpack(tmp.data_ptr(), nat.DXR_F32, B, H, W, self.num_levels,
+                                            lvl, t.data_ptr(), nat.stream_of(t))
+                if st != nat.DXR_OK:
+                    return st
+                st = lib.dxr_pyramid_pack(t.data_ptr(), B, H, W, self.num_levels, lvl,
+                                          self._buf.data_ptr(), nat.DXR_PYR_F16, nat.stream_of(t))
+                if st != nat.DXR_OK:
+                    return st
+        return nat.DXR_OK
+
+    def _launch_build(self, fmap1, fmap2, grad=False, buf=None, pyr_dt=None):
+        """One build launch into this block's pyramid buffer (or ``buf``, a
+        pyramid of ``pyr_dt``).  Returns the operand tensors the kernel read and
+        the status.
 
         f32 fmaps get a workspace from torch's caching allocator (freed when the
         build's stream work is done) for the pre-split build
@@ -544,6 +626,8 @@ class CorrBlock:
         B, D, H, W = self._geom
         lib = nat.load()
         nbytes = max(lib.dxr_build_workspace_bytes(self._in_dt, B, D, H, W), 0)
+        buf = self._buf if buf is None else buf
+        pyr_dt = self._pyr_dt if pyr_dt is None else pyr_dt
 
         def launch(f1, f2, layout, with_ws=True):
             ws = torch.empty(nbytes, dtype=torch.uint8, device=self._device) \
@@ -551,7 +635,7 @@ class CorrBlock:
             with _Launch(self._device):
                 return lib.dxr_corr_pyramid_build_ws(
                     f1.data_ptr(), f2.data_ptr(), self._in_dt, layout, B, D, H, W,
-                    self.num_levels, _sqrt_dim(D), self._buf.data_ptr(), self._pyr_dt,
+                    self.num_levels, _sqrt_dim(D), buf.data_ptr(), pyr_dt,
                     nat.DXR_BUILD_AUTO, nat.ptr(ws), nbytes if ws is not None else 0,
                     nat.stream_of(f1))
 
@@ -578,7 +662,7 @@ class CorrBlock:
         The native pyramid is stored paged (one contiguous page per build
         workgroup, include/dexiraft_corr.h); this list is materialised on first
         access by ``dxr_pyramid_unpack`` and cached.  Values are float32 (bf16
-        pyramids are widened).  The lookup never needs it.
+        and float16 pyramids are widened).  The lookup never needs it.
         """
         if self._ref_pyramid is None:
             B, D, H, W = self._geom
@@ -623,6 +707,14 @@ class CorrBlock:
     __call__.__signature__ = inspect.Signature([
         inspect.Parameter("self", inspect.Parameter.POSITIONAL_OR_KEYWORD),
         inspect.Parameter("coords", inspect.Parameter.POSITIONAL_OR_KEYWORD)])
+    # The same for the constructor (core/corr.py:13): ``pyramid_dtype`` is an
+    # extension on top of the reference's four arguments (class docstring).
+    __init__.__signature__ = inspect.Signature([
+        inspect.Parameter("self", inspect.Parameter.POSITIONAL_OR_KEYWORD),
+        inspect.Parameter("fmap1", inspect.Parameter.POSITIONAL_OR_KEYWORD),
+        inspect.Parameter("fmap2", inspect.Parameter.POSITIONAL_OR_KEYWORD),
+        inspect.Parameter("num_levels", inspect.Parameter.POSITIONAL_OR_KEYWORD, default=4),
+        inspect.Parameter("radius", inspect.Parameter.POSITIONAL_OR_KEYWORD, default=4)])
 
     def _lookup(self, c, out_dtype=None):
         B, D, H, W = self._geom

@@ -223,16 +223,21 @@ __device__ __forceinline__ void st4(float* p, float a, float b, float c, float d
 // NaN stays NaN) — the software RNE of dxr::f32_to_bf16 cost ~6 VALU per value
 // and left the bf16 build VALU-bound (round 4 PMC: 1,850 VALU per wave against
 // 64 MFMAs at KITTI B=8).
+// float16 pyramids (OT = _Float16, DXR_PYR_F16): v_cvt_f16_f32, RNE as well
+// (dxr::f32_to_f16_bits; never the round-toward-zero packed conversion).  The
+// 16-bit types are told apart by type, not by size.
 template <typename OT>
 __device__ __forceinline__ OT to_out(float v) {
-  if constexpr (sizeof(OT) == 2) return (OT)(dxr::cvt_pk_bf16(v, 0.f) & 0xffffu);
+  if constexpr (std::is_same_v<OT, _Float16>) return __builtin_bit_cast(_Float16, dxr::f32_to_f16_bits(v));
+  else if constexpr (sizeof(OT) == 2) return (OT)(dxr::cvt_pk_bf16(v, 0.f) & 0xffffu);
   else return v;
 }
 // Two values as one packed word (first in the low half).
 template <typename OT>
 __device__ __forceinline__ uint32_t to_out2(float a, float b) {
-  static_assert(sizeof(OT) == 2, "packed pairs are bf16");
-  return dxr::cvt_pk_bf16(a, b);
+  static_assert(sizeof(OT) == 2, "packed pairs are 16-bit types");
+  if constexpr (std::is_same_v<OT, _Float16>) return dxr::cvt_pk_f16_rne(a, b);
+  else return dxr::cvt_pk_bf16(a, b);
 }
 
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
@@ -1970,10 +1975,12 @@ __global__ __launch_bounds__(256) void repack_kernel(PT* __restrict__ pyr, float
     const int b = (int)(bq / N), q = (int)(bq % N);
     const long long c = dxr::cell_index(lay, b, q, y, x);
     if constexpr (UNPACK) {
-      if constexpr (sizeof(PT) == 2) ref[idx] = dxr::bf16_to_f32(pyr[c]);
+      if constexpr (std::is_same_v<PT, _Float16>) ref[idx] = (float)pyr[c];
+      else if constexpr (sizeof(PT) == 2) ref[idx] = dxr::bf16_to_f32(pyr[c]);
       else ref[idx] = pyr[c];
     } else {
-      if constexpr (sizeof(PT) == 2) pyr[c] = dxr::f32_to_bf16(ref[idx]);
+      if constexpr (std::is_same_v<PT, _Float16>) pyr[c] = (_Float16)ref[idx];   // RNE
+      else if constexpr (sizeof(PT) == 2) pyr[c] = dxr::f32_to_bf16(ref[idx]);
       else pyr[c] = ref[idx];
     }
   }
@@ -2423,7 +2430,7 @@ int check_build_args(const void* fmap1, const void* fmap2, int in_dtype, int64_t
   if (D < 1 || D > (1 << 20) || !(divisor == divisor) || divisor == 0.f) return DXR_EINVAL;
   if (B > 65535) return DXR_EINVAL;
   if ((in_dtype != DXR_F32 && in_dtype != DXR_BF16 && in_dtype != DXR_F16) ||
-      (out_dtype != DXR_F32 && out_dtype != DXR_BF16))
+      (out_dtype != DXR_F32 && out_dtype != DXR_BF16 && out_dtype != DXR_PYR_F16))
     return DXR_EINVAL;
   if (B == 0) return DXR_OK;
   if (!fmap1 || !fmap2 || !out) return DXR_EINVAL;
@@ -2475,22 +2482,48 @@ int pyramid_build(const void* fmap1, const void* fmap2, int in_dtype, int fmap_l
     // workspace.  The bf16 DMA forms' limits (D % 32 == 0, D * N * 2 < 2^31 per
     // pair, 16-byte alignment).  Anything else is unsupported: callers widen to
     // f32, as the reference does (core/raft.py:139-142).
-    if (pyr_dtype != DXR_F32 || D % 32 != 0 || D * H * W >= (1LL << 30) || !aligned16(pyramid))
+    // A DXR_PYR_F16 pyramid: the same kernel with float16 stores (at most the
+    // four fused levels, checked above).
+    if ((pyr_dtype != DXR_F32 && pyr_dtype != DXR_PYR_F16) || D % 32 != 0 ||
+        D * H * W >= (1LL << 30) || !aligned16(pyramid))
       return DXR_EUNSUPPORTED;
     const uint16_t* f1 = static_cast<const uint16_t*>(fmap1);
     const uint16_t* f2 = static_cast<const uint16_t*>(fmap2);
     float* pf = static_cast<float*>(pyramid);
+    _Float16* p16 = static_cast<_Float16*>(pyramid);
+    const bool f32p = pyr_dtype == DXR_F32;
     int st16;
     if (fmap_layout == DXR_NHWC) {
       if (!aligned16(fmap1) || !aligned16(fmap2)) return DXR_EUNSUPPORTED;
-      st16 = launch_dma_bf16_nhwc<float, DMA_F16>(f1, f2, pf, g, (int)B, stream);
+      st16 = f32p ? launch_dma_bf16_nhwc<float, DMA_F16>(f1, f2, pf, g, (int)B, stream)
+                  : launch_dma_bf16_nhwc<_Float16, DMA_F16>(f1, f2, p16, g, (int)B, stream);
     } else {
       if (workspace == nullptr || !aligned16(workspace) ||
           workspace_bytes < bf16_pack_bytes(B, D, H, W))
         return DXR_EUNSUPPORTED;
-      st16 = launch_dma_bf16_nchw<float, DMA_F16>(f1, f2, pf, g, (int)B, workspace, stream);
+      st16 = f32p ? launch_dma_bf16_nchw<float, DMA_F16>(f1, f2, pf, g, (int)B, workspace, stream)
+                  : launch_dma_bf16_nchw<_Float16, DMA_F16>(f1, f2, p16, g, (int)B, workspace,
+                                                            stream);
     }
-    return st16 != DXR_OK ? st16 : pool_extra_levels(pf, L, B, H, W, stream);
+    if (st16 != DXR_OK || !f32p) return st16;
+    return pool_extra_levels(pf, L, B, H, W, stream);
+  }
+  if (pyr_dtype == DXR_PYR_F16) {
+    // float16 pyramid from f32 fmaps: the pre-split LDS-DMA build with float16
+    // stores, under that build's own conditions; nothing else writes this type
+    // (bf16 fmaps, the workspace-less f32 kernels and DXR_BUILD_EXACT_F32 are
+    // unsupported — answered here, before any launch).
+    if (in_dtype != DXR_F32 || algo != DXR_BUILD_AUTO || D % 16 != 0 ||
+        D * H * W >= (1LL << 29) || workspace == nullptr || !aligned16(workspace) ||
+        workspace_bytes < dma_workspace_bytes(B, D, H, W) || !aligned16(pyramid))
+      return DXR_EUNSUPPORTED;
+    const float* f1 = static_cast<const float*>(fmap1);
+    const float* f2 = static_cast<const float*>(fmap2);
+    _Float16* p16 = static_cast<_Float16*>(pyramid);
+    if (fmap_layout == DXR_NCHW)
+      return launch_dma<_Float16, false>(f1, f2, p16, g, (int)B, workspace, stream);
+    if (!aligned16(f1) || !aligned16(f2)) return DXR_EUNSUPPORTED;
+    return launch_dma<_Float16, true>(f1, f2, p16, g, (int)B, workspace, stream);
   }
   int st = PROCEED;
   // f32 operands with a workspace: pre-split f16 pairs + the LDS-DMA build
@@ -2622,11 +2655,15 @@ extern "C" int dxr_pyramid_unpack(const void* pyramid, int pyr_dtype, int64_t B,
   dxr::Levels L;
   if (!dxr::make_levels(B, H, W, num_levels, &L) || level < 0 || level >= num_levels)
     return DXR_EINVAL;
-  if (pyr_dtype != DXR_F32 && pyr_dtype != DXR_BF16) return DXR_EINVAL;
+  if (pyr_dtype != DXR_F32 && pyr_dtype != DXR_BF16 && pyr_dtype != DXR_PYR_F16) return DXR_EINVAL;
   if (B == 0) return DXR_OK;
   if (!pyramid || !out) return DXR_EINVAL;
   const long long total = B * H * W * (long long)L.h[level] * L.w[level];
-  if (pyr_dtype == DXR_F32)
+  if (pyr_dtype == DXR_PYR_F16)
+    hipLaunchKernelGGL((repack_kernel<true, _Float16>), dim3(grid_for(total)), dim3(256), 0,
+                       stream, const_cast<_Float16*>(static_cast<const _Float16*>(pyramid)), out,
+                       L.lay[level], (int)B, (int)(H * W));
+  else if (pyr_dtype == DXR_F32)
     hipLaunchKernelGGL((repack_kernel<true, float>), dim3(grid_for(total)), dim3(256), 0, stream,
                        const_cast<float*>(static_cast<const float*>(pyramid)), out, L.lay[level],
                        (int)B, (int)(H * W));
@@ -2643,12 +2680,16 @@ extern "C" int dxr_pyramid_pack(const float* level_data, int64_t B, int64_t H, i
   dxr::Levels L;
   if (!dxr::make_levels(B, H, W, num_levels, &L) || level < 0 || level >= num_levels)
     return DXR_EINVAL;
-  if (pyr_dtype != DXR_F32 && pyr_dtype != DXR_BF16) return DXR_EINVAL;
+  if (pyr_dtype != DXR_F32 && pyr_dtype != DXR_BF16 && pyr_dtype != DXR_PYR_F16) return DXR_EINVAL;
   if (B == 0) return DXR_OK;
   if (!pyramid || !level_data) return DXR_EINVAL;
   const long long total = B * H * W * (long long)L.h[level] * L.w[level];
   float* src = const_cast<float*>(level_data);
-  if (pyr_dtype == DXR_F32)
+  if (pyr_dtype == DXR_PYR_F16)
+    hipLaunchKernelGGL((repack_kernel<false, _Float16>), dim3(grid_for(total)), dim3(256), 0,
+                       stream, static_cast<_Float16*>(pyramid), src, L.lay[level], (int)B,
+                       (int)(H * W));
+  else if (pyr_dtype == DXR_F32)
     hipLaunchKernelGGL((repack_kernel<false, float>), dim3(grid_for(total)), dim3(256), 0, stream,
                        static_cast<float*>(pyramid), src, L.lay[level], (int)B, (int)(H * W));
   else

@@ -84,7 +84,8 @@ LevelAddr level_addr(const dxr::LevelLayout& y) {
 
 template <typename PT>
 __device__ __forceinline__ float load_cell(const PT* p) {
-  if constexpr (sizeof(PT) == 2) return dxr::bf16_to_f32(*reinterpret_cast<const uint16_t*>(p));
+  if constexpr (std::is_same_v<PT, _Float16>) return (float)*p;   // float16 pyramid: v_cvt_f32_f16
+  else if constexpr (sizeof(PT) == 2) return dxr::bf16_to_f32(*reinterpret_cast<const uint16_t*>(p));
   else return *p;
 }
 
@@ -142,6 +143,14 @@ __device__ __forceinline__ void load_vec(const PT* p, float* v) {
   } else if constexpr (sizeof(PT) == 4 && V == 2) {
     const float2 x = *reinterpret_cast<const float2*>(p);
     v[0] = x.x; v[1] = x.y;
+  } else if constexpr (std::is_same_v<PT, _Float16> && V == 4) {
+    // float16 pyramid (PT = _Float16; bfloat16 cells are uint16_t): the bf16
+    // path's 8-byte / 4-byte gathers, widened by the hardware conversion
+    const uint2 x = *reinterpret_cast<const uint2*>(p);
+    dxr::f16x2_to_f32(x.x, v);
+    dxr::f16x2_to_f32(x.y, v + 2);
+  } else if constexpr (std::is_same_v<PT, _Float16> && V == 2) {
+    dxr::f16x2_to_f32(*reinterpret_cast<const uint32_t*>(p), v);
   } else if constexpr (sizeof(PT) == 2 && V == 4) {
     const uint2 x = *reinterpret_cast<const uint2*>(p);
     v[0] = __uint_as_float(x.x << 16); v[1] = __uint_as_float(x.x & 0xffff0000u);
@@ -579,6 +588,11 @@ __device__ __forceinline__ void qm_load_vec_buf(__amdgpu_buffer_rsrc_t rs, int q
     const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0);
     c[0] = __uint_as_float(v[0]); c[1] = __uint_as_float(v[1]);
     c[2] = __uint_as_float(v[2]); c[3] = __uint_as_float(v[3]);
+  } else if constexpr (std::is_same_v<PT, _Float16>) {
+    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+    const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, 0, 0);
+    dxr::f16x2_to_f32(v[0], c);       // an out-of-range slot reads zeros: +0.0
+    dxr::f16x2_to_f32(v[1], c + 2);
   } else {
     typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
     const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, 0, 0);
@@ -1530,11 +1544,17 @@ int corr_lookup_impl(const void* pyramid, int pyr_dtype, int64_t B, int64_t H, i
   g.levels = num_levels;
   g.cout = num_levels * rd * rd;
   for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
+#ifdef DXR_LOOKUP_PYR16_TU   // float16 cells, and only them (corr_lookup_pyr16.hip)
+  if (pyr_dtype == DXR_PYR_F16)
+    return launch_lookup(static_cast<const _Float16*>(pyramid), coords, out, g, (int)B, radius,
+                         stream);
+#else
   if (pyr_dtype == DXR_F32)
     return launch_lookup(static_cast<const float*>(pyramid), coords, out, g, (int)B, radius, stream);
   if (pyr_dtype == DXR_BF16)
     return launch_lookup(static_cast<const uint16_t*>(pyramid), coords, out, g, (int)B, radius,
                          stream);
+#endif
   return DXR_EINVAL;
 }
 
@@ -1558,18 +1578,55 @@ int corr_lookup_conv1x1_impl(const void* pyramid, int pyr_dtype, int64_t B, int6
   g.cout = num_levels * rd * rd;
   for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
   const float4* wpl = static_cast<const float4*>(weight_packed);
+#ifdef DXR_LOOKUP_PYR16_TU
+  if (pyr_dtype == DXR_PYR_F16)
+    return launch_lookup_conv1x1(static_cast<const _Float16*>(pyramid), coords, wpl, bias, out, g,
+                                 (int)B, radius, (int)cout, relu, stream);
+#else
   if (pyr_dtype == DXR_F32)
     return launch_lookup_conv1x1(static_cast<const float*>(pyramid), coords, wpl, bias, out, g,
                                  (int)B, radius, (int)cout, relu, stream);
   if (pyr_dtype == DXR_BF16)
     return launch_lookup_conv1x1(static_cast<const uint16_t*>(pyramid), coords, wpl, bias, out, g,
                                  (int)B, radius, (int)cout, relu, stream);
+#endif
   return DXR_EINVAL;
 }
 
 }  // namespace
 
-#ifdef DXR_LOOKUP_OUT16_TU
+#if defined(DXR_LOOKUP_PYR16_TU)
+// corr_lookup_pyr16.hip: this file's templates with float16 pyramid cells (every
+// output type), and nothing else of it.
+int dxr::lookup_pyr16(const void* pyramid, int out_flag, int64_t B, int64_t H, int64_t W,
+                      int num_levels, int radius, const float* coords, void* out,
+                      hipStream_t stream) {
+  if (out_flag == DXR_OUT_F16)
+    return corr_lookup_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
+                            static_cast<_Float16*>(out), stream);
+  if (out_flag == DXR_OUT_BF16)
+    return corr_lookup_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
+                            static_cast<__bf16*>(out), stream);
+  return corr_lookup_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
+                          static_cast<float*>(out), stream);
+}
+
+int dxr::lookup_conv1x1_pyr16(const void* pyramid, int out_flag, int64_t B, int64_t H, int64_t W,
+                              int num_levels, int radius, const float* coords,
+                              const void* weight_packed, const float* bias, int64_t cout, int relu,
+                              void* out, hipStream_t stream) {
+  if (out_flag == DXR_OUT_F16)
+    return corr_lookup_conv1x1_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
+                                    weight_packed, bias, cout, relu, static_cast<_Float16*>(out),
+                                    stream);
+  if (out_flag == DXR_OUT_BF16)
+    return corr_lookup_conv1x1_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
+                                    weight_packed, bias, cout, relu, static_cast<__bf16*>(out),
+                                    stream);
+  return corr_lookup_conv1x1_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
+                                  weight_packed, bias, cout, relu, static_cast<float*>(out), stream);
+}
+#elif defined(DXR_LOOKUP_OUT16_TU)
 // corr_lookup_out16.hip: this file's templates with the 16-bit output types, and
 // nothing else of it.
 int dxr::lookup_out16(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H,
@@ -1665,7 +1722,7 @@ extern "C" int dxr_alt_volume_lookup(const float* volumes, const float* coords, 
 
 namespace {
 // The output dtype flag of dxr_corr_lookup / dxr_corr_lookup_conv1x1 (DXR_OUT_F16,
-// DXR_OUT_BF16, or-ed onto a DXR_F32 / DXR_BF16 pyr_dtype): splits it off.  False
+// DXR_OUT_BF16, or-ed onto a DXR_F32 / DXR_BF16 / DXR_PYR_F16 pyr_dtype): splits it off.  False
 // (DXR_EINVAL) for both flags, any other high bit, a flag on another low value,
 // or a flagged `out` that is not 2-byte aligned.  Unflagged values pass through
 // to the callers' own checks.
@@ -1675,7 +1732,7 @@ bool split_out_dtype(int* pyr_dtype, int* out_flag, const void* out) {
   if (hi == 0) return true;
   if (hi != DXR_OUT_F16 && hi != DXR_OUT_BF16) return false;
   const int lo = *pyr_dtype & 0xff;
-  if (lo != DXR_F32 && lo != DXR_BF16) return false;
+  if (lo != DXR_F32 && lo != DXR_BF16 && lo != DXR_PYR_F16) return false;
   if (reinterpret_cast<uintptr_t>(out) & 1) return false;
   *pyr_dtype = lo;
   *out_flag = hi;
@@ -1688,6 +1745,8 @@ extern "C" int dxr_corr_lookup(const void* pyramid, int pyr_dtype, int64_t B, in
                                float* out, hipStream_t stream) {
   int out_flag;
   if (!split_out_dtype(&pyr_dtype, &out_flag, out)) return DXR_EINVAL;
+  if (pyr_dtype == DXR_PYR_F16)   // float16 cells: their own translation unit, every output type
+    return dxr::lookup_pyr16(pyramid, out_flag, B, H, W, num_levels, radius, coords, out, stream);
   if (out_flag)
     return dxr::lookup_out16(pyramid, pyr_dtype, out_flag, B, H, W, num_levels, radius, coords, out,
                              stream);
@@ -1820,6 +1879,9 @@ extern "C" int dxr_corr_lookup_conv1x1(const void* pyramid, int pyr_dtype, int64
                                        int relu, float* out, hipStream_t stream) {
   int out_flag;
   if (!split_out_dtype(&pyr_dtype, &out_flag, out)) return DXR_EINVAL;
+  if (pyr_dtype == DXR_PYR_F16)
+    return dxr::lookup_conv1x1_pyr16(pyramid, out_flag, B, H, W, num_levels, radius, coords,
+                                     weight_packed, bias, cout, relu, out, stream);
   if (out_flag)
     return dxr::lookup_conv1x1_out16(pyramid, pyr_dtype, out_flag, B, H, W, num_levels, radius,
                                      coords, weight_packed, bias, cout, relu, out, stream);

@@ -32,6 +32,16 @@ int lookup_conv1x1_out16(const void* pyramid, int pyr_dtype, int out_flag, int64
                          const void* weight_packed, const float* bias, int64_t cout, int relu,
                          void* out, hipStream_t stream);
 
+// The same two calls on a float16 pyramid (pyr_dtype DXR_PYR_F16, split off and
+// validated by the entry points; out_flag 0: float32 `out`, else as above).
+// Defined in corr_lookup_pyr16.hip, the only translation unit that instantiates
+// the lookup kernels with the float16 cell type.
+int lookup_pyr16(const void* pyramid, int out_flag, int64_t B, int64_t H, int64_t W, int num_levels,
+                 int radius, const float* coords, void* out, hipStream_t stream);
+int lookup_conv1x1_pyr16(const void* pyramid, int out_flag, int64_t B, int64_t H, int64_t W,
+                         int num_levels, int radius, const float* coords, const void* weight_packed,
+                         const float* bias, int64_t cout, int relu, void* out, hipStream_t stream);
+
 // ---------------------------------------------------------------------------
 // Pyramid layout ("paged" correlation volume).
 //
@@ -116,6 +126,31 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
   if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
+}
+
+// Float16 pyramid cells (DXR_PYR_F16).  The element type is _Float16, distinct
+// from the uint16_t of bfloat16 pyramids, so templates pick the conversion by
+// type.  Widening is the hardware v_cvt_f32_f16 (exact, subnormals included).
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void f16x2_to_f32(uint32_t w, float* v) {
+  const f16x2_t h = __builtin_bit_cast(f16x2_t, w);
+  v[0] = (float)h[0];
+  v[1] = (float)h[1];
+}
+
+// Round-to-nearest-even f32 -> f16 (v_cvt_f16_f32: overflow to +-inf, subnormals
+// kept, NaN stays NaN); torch's .half().  The packed v_cvt_pkrtz_f16_f32 rounds
+// toward zero and must not be used for stored cells.  The value is pinned as an
+// f32 register first so that no producing multiply-add is folded into a
+// single-rounding mixed-precision instruction.
+__device__ __forceinline__ uint16_t f32_to_f16_bits(float f) {
+  asm volatile("" : "+v"(f));
+  return __builtin_bit_cast(uint16_t, (_Float16)f);
+}
+__device__ __forceinline__ uint32_t cvt_pk_f16_rne(float a, float b) {
+  return (uint32_t)f32_to_f16_bits(a) | ((uint32_t)f32_to_f16_bits(b) << 16);
 }
 
 // Exact hi/mid/lo split of 8 floats into three 8 x bf16 MFMA operands
