@@ -187,26 +187,49 @@ int64_t dxr_pyramid_level_offset(int64_t B, int64_t H, int64_t W, int level);
  * DXR_EUNSUPPORTED before any launch; such a pyramid can be made from a DXR_F32
  * one, level by level, with dxr_pyramid_unpack + dxr_pyramid_pack.
  *
- * Kernels by request (both build entry points; tests/test_gpu_parity.py
- * test_build_kernel_by_request runs each one by name against the oracle):
- *   f32, workspace, AUTO, D % 16 == 0   split_pairs_kernel + corr_build_dma_kernel
- *                                        (CorrBlock's path; NCHW or NHWC)
- *   f32, no workspace, AUTO, D % 16 == 0, even W
- *                                        corr_build_split_kernel (round-2 register
- *                                        split; the documented fallback for callers
- *                                        that cannot provide a workspace)
- *   f32, EXACT_F32 or D % 16 != 0 (or odd W without a workspace)
- *                                        corr_build_f32_kernel (exact-f32 MFMA)
- *   bf16 NCHW, workspace, D % 32 == 0   pack_bf16_kernel + corr_build_dma_kernel
- *   bf16 NHWC, D % 32 == 0              corr_build_dma_kernel (rows read in place)
- *   bf16 NCHW, no workspace, W % 4 == 0 corr_build_bf16_q2_kernel
- *   bf16 otherwise                      corr_build_bf16_kernel (one query block)
- *   f16 NCHW, workspace, D % 32 == 0    pack_bf16_kernel + corr_build_dma_kernel
- *                                        (f16 records, f32 pyramid)
- *   f16 NHWC, D % 32 == 0               corr_build_dma_kernel (rows read in place)
- *   f16 otherwise                       none: DXR_EUNSUPPORTED
- *   DXR_PYR_F16                         the f32 + workspace and the two f16 rows above,
- *                                        with float16 stores; otherwise DXR_EUNSUPPORTED
+ * Kernels by request (both build entry points).  csrc/build_plan.h is this
+ * table's implementation: its plan_build() answers every refusal and names the
+ * kernel before anything is launched, and tests/test_build_plan.py checks it
+ * against these rows one by one on a CPU (tests/test_gpu_parity.py
+ * test_build_kernel_by_request runs the kernels against the oracle).
+ * First, for every request: invalid arguments are DXR_EINVAL (B == 0 is DXR_OK
+ * before the pointers are looked at); more than 4 levels with a pyramid that is
+ * not DXR_F32, and DXR_BUILD_EXACT_F32 with fmaps that are not f32, are
+ * DXR_EUNSUPPORTED.  Then the first row that matches, top to bottom.
+ * "workspace": non-null, 16-byte aligned and at least dxr_build_workspace_bytes
+ * (anything less counts as none); "aligned": 16-byte aligned.
+ *   f16 fmaps, f32 or float16 pyramid, D % 32 == 0, D*H*W < 2^30, pyramid aligned:
+ *     NHWC, fmaps aligned               corr_build_dma_kernel (rows read in place)
+ *     NCHW, workspace                   pack_bf16_kernel + corr_build_dma_kernel
+ *   f16 fmaps otherwise                 none: DXR_EUNSUPPORTED
+ *   f32, workspace, AUTO, D % 16 == 0, D*H*W < 2^29, pyramid aligned (CorrBlock's path):
+ *     NCHW                              split_pairs_kernel<NCHW> + corr_build_dma_kernel
+ *     NHWC, fmaps aligned               split_pairs_kernel<NHWC> + corr_build_dma_kernel
+ *   float16 pyramid otherwise           none: DXR_EUNSUPPORTED
+ *   bf16 NCHW, workspace, D % 32 == 0, D*H*W < 2^30, pyramid aligned, <= 4 levels
+ *                                       pack_bf16_kernel + corr_build_dma_kernel
+ *   bf16 NHWC, D % 32 == 0, D*H*W < 2^30, fmaps and pyramid aligned
+ *                                       corr_build_dma_kernel (rows read in place)
+ *   bf16 NHWC otherwise                 none: DXR_EUNSUPPORTED
+ *   f32 NHWC, AUTO, D % 16 == 0, D*H*W < 2^29, even W, fmaps and pyramid aligned
+ *                                       corr_build_split_kernel<NHWC>
+ *   f32 NHWC otherwise                  none: DXR_EUNSUPPORTED
+ *   f32 NCHW, AUTO, D % 16 == 0, D*H*W < 2^29 (round-2 register split; the
+ *   documented fallback for callers that cannot provide a workspace):
+ *     W % 4 == 0, fmaps and pyramid aligned
+ *                                       corr_build_split_kernel<float4>
+ *     even W, fmaps 8-byte aligned, pyramid aligned
+ *                                       corr_build_split_kernel<float2>
+ *   f32 NCHW otherwise (EXACT_F32, D % 16 != 0, odd W, alignment; exact-f32 MFMA):
+ *     W % 4 == 0, fmaps and pyramid aligned
+ *                                       corr_build_f32_kernel<vec>
+ *     else                              corr_build_f32_kernel<scalar>
+ *   bf16 NCHW, W % 4 == 0, fmaps 8-byte aligned, pyramid aligned, D*H*W < 2^30
+ *                                       corr_build_bf16_q2_kernel
+ *   bf16 NCHW otherwise                 corr_build_bf16_kernel (one query block)
+ * Last: every kernel but the two 16-bit corr_build_dma_kernel rows (1-D grids)
+ * runs on a grid with ceil(H*W / 128) rows; more than 65535 are DXR_EINVAL.
+ * Levels beyond 4 follow as f32 pooling passes.
  */
 int dxr_corr_pyramid_build(const void* fmap1, const void* fmap2, int in_dtype,
                            int fmap_layout, int64_t B, int64_t D, int64_t H,
@@ -219,7 +242,8 @@ int dxr_corr_pyramid_build(const void* fmap1, const void* fmap2, int in_dtype,
  * D x H x W fmaps of in_dtype (0: that request needs none; -1: bad geometry):
  * f32 with D % 16 == 0 the pre-split operands, bf16 with D % 32 == 0 the pack
  * pass's blocked copies of NCHW fmaps (channels-last bf16 fmaps need none);
- * f16 as bf16 (the same 16-bit pack pass).
+ * f16 as bf16 (the same 16-bit pack pass).  A size beyond int64 is -1 too
+ * (only with B > 65535 or D*H*W >= 2^30, where no build takes a workspace).
  * ABI 6.
  */
 int64_t dxr_build_workspace_bytes(int in_dtype, int64_t B, int64_t D, int64_t H,

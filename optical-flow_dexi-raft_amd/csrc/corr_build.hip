@@ -28,6 +28,7 @@
 #include <cmath>
 #include <type_traits>
 
+#include "build_plan.h"
 #include "dxr_common.h"
 
 namespace {
@@ -2103,7 +2104,6 @@ template <bool PAGED, typename OT>
 int launch_f32(bool vec, const float* f1, const float* f2, OT* pyr, const BuildGeom& g, int B,
                hipStream_t stream) {
   const dim3 grid = build_grid(g, B);
-  if (grid.y > 65535) return DXR_EINVAL;
   const bool div = g.recip == 0.f;
   if (vec && div)
     hipLaunchKernelGGL((corr_build_f32_kernel<true, 16, PAGED, OT, 3, true>), grid, dim3(NT), 0,
@@ -2143,7 +2143,6 @@ template <typename OT>
 int launch_build_bf16(bool vec, const uint16_t* f1, const uint16_t* f2, OT* pyr,
                       const BuildGeom& g, int B, hipStream_t stream) {
   const dim3 grid = build_grid(g, B);
-  if (grid.y > 65535) return DXR_EINVAL;
   const bool div = g.recip == 0.f;
   if (vec) {
     // two query blocks per workgroup, XCD-banded group order
@@ -2168,11 +2167,10 @@ int launch_build_bf16(bool vec, const uint16_t* f1, const uint16_t* f2, OT* pyr,
 // bf16 split) at 3 waves/SIMD: r02 Sintel 134-142 us against 151-154 for the
 // 3-way bf16 split at 4 waves/SIMD, and 0.4-0.8x its max error against f64
 // (scripts/xp_accuracy.py).
-template <typename OT, int BV, bool NHWC = false>
+template <int BV, bool NHWC = false, typename OT>
 int launch_split(const float* f1, const float* f2, OT* pyr, const BuildGeom& g, int B,
                  hipStream_t stream) {
   const dim3 grid = build_grid(g, B);
-  if (grid.y > 65535) return DXR_EINVAL;
   if (g.recip == 0.f)
     hipLaunchKernelGGL((corr_build_split_kernel<OT, true, 3, BV, NHWC, true>), grid, dim3(NT),
                        0, stream, f1, f2, pyr, g);
@@ -2257,18 +2255,13 @@ void launch_dma_kernel(const dim3& rg, const BuildGeom& g, int B, hipStream_t st
   }
 }
 
-// Pre-split + LDS-DMA f32 build (round 3): workspace = SP1 | SP2 | E1 | E2.
-long long align256(long long x) { return (x + 255) & ~255LL; }
-long long dma_workspace_bytes(long long B, long long D, long long H, long long W) {
-  const long long N = H * W;
-  return 2 * align256(B * D * N * 4) + 2 * align256(B * N * 4);
-}
+// Pre-split + LDS-DMA f32 build (round 3): workspace = SP1 | SP2 | E1 | E2
+// (dxr::dma_workspace_bytes, build_plan.h).
+using dxr::align256;
 
-template <typename OT, bool NHWC>
+template <bool NHWC, typename OT>
 int launch_dma(const float* f1, const float* f2, OT* pyr, BuildGeom g, int B, void* ws,
                hipStream_t stream, int tail = DMA_TAIL_DEFAULT) {
-  const dim3 grid = build_grid(g, B);
-  if (grid.y > 65535) return DXR_EINVAL;
   const long long N = g.N, spb = align256((long long)B * g.D * N * 4), eb = align256((long long)B * N * 4);
   uint8_t* w = static_cast<uint8_t*>(ws);
   uint8_t* sp1 = w;
@@ -2294,7 +2287,7 @@ int launch_dma(const float* f1, const float* f2, OT* pyr, BuildGeom g, int B, vo
 // 16-bit operand records by LDS-DMA (corr_build_dma_kernel<.., OPK>, OPK =
 // DMA_BF16 or DMA_F16): channels-last bf16 / f16 fmaps are read in place (pixel
 // stride D * 2 B, stage stride 64 B).
-template <typename OT, int OPK = DMA_BF16>
+template <int OPK = DMA_BF16, typename OT>
 int launch_dma_bf16_nhwc(const uint16_t* f1, const uint16_t* f2, OT* pyr, BuildGeom g, int B,
                          hipStream_t stream, int tail = DMA_TAIL_DEFAULT) {
   const dim3 rg = dma_grid(g, B, stream, tail);
@@ -2359,13 +2352,9 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(const uint16_t* __restri
   }
 }
 
-long long bf16_pack_bytes(long long B, long long D, long long H, long long W) {
-  return 2 * align256(B * D * H * W * 2);
-}
-
 // NCHW bf16 fmaps with a workspace: pack pass + the bf16 DMA build
 // (blocked records: pixel stride 64 B, stage stride N * 64 B).
-template <typename OT, int OPK = DMA_BF16>
+template <int OPK = DMA_BF16, typename OT>
 int launch_dma_bf16_nchw(const uint16_t* f1, const uint16_t* f2, OT* pyr, BuildGeom g, int B,
                          void* ws, hipStream_t stream, int tail = DMA_TAIL_DEFAULT) {
   const long long half = align256((long long)B * g.D * g.N * 2);
@@ -2384,21 +2373,6 @@ int launch_dma_bf16_nchw(const uint16_t* f1, const uint16_t* f2, OT* pyr, BuildG
                               (const int*)nullptr, (const int*)nullptr, pyr, (const float*)nullptr,
                               (const float*)nullptr, 0, 0, 64, g.N * 64);
   return dxr::launch_status();
-}
-
-// f32 fmaps: the split build when its layout conditions hold (D % 16 == 0;
-// float4 target units for W % 4 == 0, float2 units for even W), else — or on
-// request (DXR_BUILD_EXACT_F32) — the exact-f32 MFMA build.
-template <typename OT>
-int launch_build_f32(bool vec, const float* f1, const float* f2, OT* pyr, const BuildGeom& g,
-                     int B, int algo, hipStream_t stream) {
-  if (algo == DXR_BUILD_AUTO && g.D % 16 == 0 && (long long)g.D * g.N < (1LL << 29)) {
-    if (vec) return launch_split<OT, 4>(f1, f2, pyr, g, B, stream);
-    if (g.W % 2 == 0 && ((uintptr_t)f1 % 8) == 0 && ((uintptr_t)f2 % 8) == 0 &&
-        ((uintptr_t)pyr % 16) == 0)
-      return launch_split<OT, 2>(f1, f2, pyr, g, B, stream);
-  }
-  return launch_f32<true>(vec, f1, f2, pyr, g, B, stream);
 }
 
 BuildGeom make_geom(int64_t D, int64_t H, int64_t W, float divisor, const dxr::Levels& L) {
@@ -2421,20 +2395,17 @@ BuildGeom make_geom(int64_t D, int64_t H, int64_t W, float divisor, const dxr::L
   return g;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
-constexpr int PROCEED = -100;
-
-int check_build_args(const void* fmap1, const void* fmap2, int in_dtype, int64_t B, int64_t D,
-                     float divisor, const void* out, int out_dtype) {
-  if (D < 1 || D > (1 << 20) || !(divisor == divisor) || divisor == 0.f) return DXR_EINVAL;
-  if (B > 65535) return DXR_EINVAL;
-  if ((in_dtype != DXR_F32 && in_dtype != DXR_BF16 && in_dtype != DXR_F16) ||
-      (out_dtype != DXR_F32 && out_dtype != DXR_BF16 && out_dtype != DXR_PYR_F16))
-    return DXR_EINVAL;
-  if (B == 0) return DXR_OK;
-  if (!fmap1 || !fmap2 || !out) return DXR_EINVAL;
-  return PROCEED;
+// Call f with the pyramid as a pointer to its cell type: float, uint16_t
+// (bfloat16 bits) or _Float16.  BF16 / F16 false: a path that has no kernel
+// storing that type, so none gets instantiated for it (the planner never sends
+// such a request there).
+template <bool BF16 = true, bool F16 = true, typename F>
+int with_cells(int pyr_dtype, void* pyramid, F&& f) {
+  if constexpr (BF16)
+    if (pyr_dtype == DXR_BF16) return f(static_cast<uint16_t*>(pyramid));
+  if constexpr (F16)
+    if (pyr_dtype == DXR_PYR_F16) return f(static_cast<_Float16*>(pyramid));
+  return f(static_cast<float*>(pyramid));
 }
 
 }  // namespace
@@ -2461,160 +2432,81 @@ int pool_extra_levels(float* pyr, const dxr::Levels& L, int64_t B, int64_t H, in
   return DXR_OK;
 }
 
+// Plan (build_plan.h: every check and the choice of kernel), launch, pool.
 int pyramid_build(const void* fmap1, const void* fmap2, int in_dtype, int fmap_layout, int64_t B,
                   int64_t D, int64_t H, int64_t W, int num_levels, float divisor, void* pyramid,
                   int pyr_dtype, int algo, void* workspace, int64_t workspace_bytes,
                   hipStream_t stream) {
+  const dxr::BuildRequest rq{in_dtype, fmap_layout, B, D, H, W, num_levels, divisor, pyr_dtype,
+                             algo, (uintptr_t)fmap1, (uintptr_t)fmap2, (uintptr_t)pyramid,
+                             (uintptr_t)workspace, workspace_bytes};
+  dxr::BuildPlan plan;
+  int st = dxr::plan_build(rq, &plan);
+  if (st != DXR_OK || plan.path == dxr::BUILD_NONE) return st;
   dxr::Levels L;
-  if (!dxr::make_levels(B, H, W, num_levels, &L)) return DXR_EINVAL;
-  if (fmap_layout != DXR_NCHW && fmap_layout != DXR_NHWC) return DXR_EINVAL;
-  if (algo != DXR_BUILD_AUTO && algo != DXR_BUILD_EXACT_F32) return DXR_EINVAL;
-  const int chk = check_build_args(fmap1, fmap2, in_dtype, B, D, divisor, pyramid, pyr_dtype);
-  if (chk != PROCEED) return chk;
-  // Levels beyond the fused four are pooled by f32 passes: f32 pyramids only.
-  if (L.n > dxr::TILED_LEVELS && pyr_dtype != DXR_F32) return DXR_EUNSUPPORTED;
-  if (algo == DXR_BUILD_EXACT_F32 && in_dtype != DXR_F32) return DXR_EUNSUPPORTED;
+  dxr::make_levels(B, H, W, num_levels, &L);   // holds: the planner checked the geometry
   const BuildGeom g = make_geom(D, H, W, divisor, L);
-  if (in_dtype == DXR_F16) {
-    // float16 operands (mixed-precision encoders): the DMA build on f16 records,
-    // one MFMA product per channel pair, into an f32 pyramid.  Channels-last
-    // fmaps are read in place; NCHW fmaps go through the 16-bit pack pass into the
-    // workspace.  The bf16 DMA forms' limits (D % 32 == 0, D * N * 2 < 2^31 per
-    // pair, 16-byte alignment).  Anything else is unsupported: callers widen to
-    // f32, as the reference does (core/raft.py:139-142).
-    // A DXR_PYR_F16 pyramid: the same kernel with float16 stores (at most the
-    // four fused levels, checked above).
-    if ((pyr_dtype != DXR_F32 && pyr_dtype != DXR_PYR_F16) || D % 32 != 0 ||
-        D * H * W >= (1LL << 30) || !aligned16(pyramid))
-      return DXR_EUNSUPPORTED;
-    const uint16_t* f1 = static_cast<const uint16_t*>(fmap1);
-    const uint16_t* f2 = static_cast<const uint16_t*>(fmap2);
-    float* pf = static_cast<float*>(pyramid);
-    _Float16* p16 = static_cast<_Float16*>(pyramid);
-    const bool f32p = pyr_dtype == DXR_F32;
-    int st16;
-    if (fmap_layout == DXR_NHWC) {
-      if (!aligned16(fmap1) || !aligned16(fmap2)) return DXR_EUNSUPPORTED;
-      st16 = f32p ? launch_dma_bf16_nhwc<float, DMA_F16>(f1, f2, pf, g, (int)B, stream)
-                  : launch_dma_bf16_nhwc<_Float16, DMA_F16>(f1, f2, p16, g, (int)B, stream);
-    } else {
-      if (workspace == nullptr || !aligned16(workspace) ||
-          workspace_bytes < bf16_pack_bytes(B, D, H, W))
-        return DXR_EUNSUPPORTED;
-      st16 = f32p ? launch_dma_bf16_nchw<float, DMA_F16>(f1, f2, pf, g, (int)B, workspace, stream)
-                  : launch_dma_bf16_nchw<_Float16, DMA_F16>(f1, f2, p16, g, (int)B, workspace,
-                                                            stream);
-    }
-    if (st16 != DXR_OK || !f32p) return st16;
-    return pool_extra_levels(pf, L, B, H, W, stream);
+  const int nb = (int)B;
+  const float* a = static_cast<const float*>(fmap1);
+  const float* b = static_cast<const float*>(fmap2);
+  const uint16_t* ah = static_cast<const uint16_t*>(fmap1);   // bf16 or f16 bits
+  const uint16_t* bh = static_cast<const uint16_t*>(fmap2);
+  const bool f16 = plan.operand == DXR_F16;
+  // the cell types a path has kernels for: all three, f32 + bf16, f32 + float16
+  const auto any = [&](auto f) { return with_cells<true, true>(plan.cells, pyramid, f); };
+  const auto f32_bf16 = [&](auto f) { return with_cells<true, false>(plan.cells, pyramid, f); };
+  const auto f32_f16 = [&](auto f) { return with_cells<false, true>(plan.cells, pyramid, f); };
+  switch (plan.path) {
+    case dxr::BUILD_DMA_F32_NCHW:   // NCHW operands are read as scalars by the split pass
+      st = any([&](auto* p) { return launch_dma<false>(a, b, p, g, nb, workspace, stream); });
+      break;
+    case dxr::BUILD_DMA_F32_NHWC:   // NHWC as float4
+      st = any([&](auto* p) { return launch_dma<true>(a, b, p, g, nb, workspace, stream); });
+      break;
+    case dxr::BUILD_SPLIT_F4:
+      st = f32_bf16([&](auto* p) { return launch_split<4>(a, b, p, g, nb, stream); });
+      break;
+    case dxr::BUILD_SPLIT_F2:
+      st = f32_bf16([&](auto* p) { return launch_split<2>(a, b, p, g, nb, stream); });
+      break;
+    case dxr::BUILD_SPLIT_NHWC:
+      st = f32_bf16([&](auto* p) { return launch_split<4, true>(a, b, p, g, nb, stream); });
+      break;
+    case dxr::BUILD_EXACT_VEC:
+    case dxr::BUILD_EXACT_SCALAR:
+      st = f32_bf16([&](auto* p) {
+        return launch_f32<true>(plan.path == dxr::BUILD_EXACT_VEC, a, b, p, g, nb, stream);
+      });
+      break;
+    case dxr::BUILD_PACK_DMA16:   // f16 records: f32 or float16 cells; bf16 records: f32 or bf16
+      st = f16 ? f32_f16([&](auto* p) {
+        return launch_dma_bf16_nchw<DMA_F16>(ah, bh, p, g, nb, workspace, stream);
+      }) : f32_bf16([&](auto* p) {
+        return launch_dma_bf16_nchw<DMA_BF16>(ah, bh, p, g, nb, workspace, stream);
+      });
+      break;
+    case dxr::BUILD_DMA16_NHWC:
+      st = f16 ? f32_f16([&](auto* p) {
+        return launch_dma_bf16_nhwc<DMA_F16>(ah, bh, p, g, nb, stream);
+      }) : f32_bf16([&](auto* p) {
+        return launch_dma_bf16_nhwc<DMA_BF16>(ah, bh, p, g, nb, stream);
+      });
+      break;
+    case dxr::BUILD_BF16_Q2:
+    case dxr::BUILD_BF16:
+      st = f32_bf16([&](auto* p) {
+        return launch_build_bf16(plan.path == dxr::BUILD_BF16_Q2, ah, bh, p, g, nb, stream);
+      });
+      break;
   }
-  if (pyr_dtype == DXR_PYR_F16) {
-    // float16 pyramid from f32 fmaps: the pre-split LDS-DMA build with float16
-    // stores, under that build's own conditions; nothing else writes this type
-    // (bf16 fmaps, the workspace-less f32 kernels and DXR_BUILD_EXACT_F32 are
-    // unsupported — answered here, before any launch).
-    if (in_dtype != DXR_F32 || algo != DXR_BUILD_AUTO || D % 16 != 0 ||
-        D * H * W >= (1LL << 29) || workspace == nullptr || !aligned16(workspace) ||
-        workspace_bytes < dma_workspace_bytes(B, D, H, W) || !aligned16(pyramid))
-      return DXR_EUNSUPPORTED;
-    const float* f1 = static_cast<const float*>(fmap1);
-    const float* f2 = static_cast<const float*>(fmap2);
-    _Float16* p16 = static_cast<_Float16*>(pyramid);
-    if (fmap_layout == DXR_NCHW)
-      return launch_dma<_Float16, false>(f1, f2, p16, g, (int)B, workspace, stream);
-    if (!aligned16(f1) || !aligned16(f2)) return DXR_EUNSUPPORTED;
-    return launch_dma<_Float16, true>(f1, f2, p16, g, (int)B, workspace, stream);
-  }
-  int st = PROCEED;
-  // f32 operands with a workspace: pre-split f16 pairs + the LDS-DMA build
-  // (any W; D % 16 == 0; NHWC rows 16-byte aligned).
-  const bool dma_ok = in_dtype == DXR_F32 && algo == DXR_BUILD_AUTO && D % 16 == 0 &&
-                      D * H * W < (1LL << 29) && workspace != nullptr && aligned16(workspace) &&
-                      workspace_bytes >= dma_workspace_bytes(B, D, H, W) && aligned16(pyramid);
-  if (dma_ok) {
-    const float* f1 = static_cast<const float*>(fmap1);
-    const float* f2 = static_cast<const float*>(fmap2);
-    float* pf = static_cast<float*>(pyramid);
-    uint16_t* ph = static_cast<uint16_t*>(pyramid);
-    const bool f32p = pyr_dtype == DXR_F32;
-    // NCHW operands are read as scalars by the split pass; NHWC as float4
-    if (fmap_layout == DXR_NCHW)
-      st = f32p ? launch_dma<float, false>(f1, f2, pf, g, (int)B, workspace, stream)
-                : launch_dma<uint16_t, false>(f1, f2, ph, g, (int)B, workspace, stream);
-    else if (aligned16(f1) && aligned16(f2))
-      st = f32p ? launch_dma<float, true>(f1, f2, pf, g, (int)B, workspace, stream)
-                : launch_dma<uint16_t, true>(f1, f2, ph, g, (int)B, workspace, stream);
-  }
-  // bf16 NCHW operands with a workspace: pack pass + the bf16 DMA build (D % 32,
-  // D * N * 2 < 2^31 per pair)
-  if (st == PROCEED && in_dtype == DXR_BF16 && fmap_layout == DXR_NCHW && D % 32 == 0 &&
-      D * H * W < (1LL << 30) && L.n <= dxr::TILED_LEVELS && workspace != nullptr &&
-      aligned16(workspace) && workspace_bytes >= bf16_pack_bytes(B, D, H, W) &&
-      aligned16(pyramid)) {
-    const uint16_t* f1 = static_cast<const uint16_t*>(fmap1);
-    const uint16_t* f2 = static_cast<const uint16_t*>(fmap2);
-    st = pyr_dtype == DXR_F32
-             ? launch_dma_bf16_nchw(f1, f2, static_cast<float*>(pyramid), g, (int)B, workspace,
-                                    stream)
-             : launch_dma_bf16_nchw(f1, f2, static_cast<uint16_t*>(pyramid), g, (int)B, workspace,
-                                    stream);
-  }
-  if (st != PROCEED) {
-    // done by a DMA build
-  } else if (fmap_layout == DXR_NHWC && in_dtype == DXR_BF16) {
-    // channels-last bf16 operands (the bf16 mode's encoders, core/extractor.py:168-192):
-    // the two-block bf16 build's NHWC form, bit-identical to the NCHW build;
-    // D % 32 == 0 (whole 32-channel stages) and 16-byte aligned pixels
-    if (D % 32 != 0 || D * H * W >= (1LL << 30) || !aligned16(fmap1) || !aligned16(fmap2) ||
-        !aligned16(pyramid))
-      return DXR_EUNSUPPORTED;
-    const uint16_t* f1 = static_cast<const uint16_t*>(fmap1);
-    const uint16_t* f2 = static_cast<const uint16_t*>(fmap2);
-    st = pyr_dtype == DXR_F32
-             ? launch_dma_bf16_nhwc(f1, f2, static_cast<float*>(pyramid), g, (int)B, stream)
-             : launch_dma_bf16_nhwc(f1, f2, static_cast<uint16_t*>(pyramid), g, (int)B, stream);
-  } else if (fmap_layout == DXR_NHWC) {
-    // channels-last f32 operands: the split build's NHWC form, where the NCHW build
-    // would also be the split build (f32 fmaps, D % 16 == 0, even W: same bits),
-    // with 16-byte aligned rows; other requests are unsupported (callers transpose)
-    if (algo != DXR_BUILD_AUTO || D % 16 != 0 || W % 2 != 0 ||
-        D * H * W >= (1LL << 29) || !aligned16(fmap1) || !aligned16(fmap2) || !aligned16(pyramid))
-      return DXR_EUNSUPPORTED;
-    const float* f1 = static_cast<const float*>(fmap1);
-    const float* f2 = static_cast<const float*>(fmap2);
-    st = pyr_dtype == DXR_F32
-             ? launch_split<float, 4, true>(f1, f2, static_cast<float*>(pyramid), g, (int)B, stream)
-             : launch_split<uint16_t, 4, true>(f1, f2, static_cast<uint16_t*>(pyramid), g, (int)B,
-                                               stream);
-  } else if (in_dtype == DXR_F32) {
-    const float* f1 = static_cast<const float*>(fmap1);
-    const float* f2 = static_cast<const float*>(fmap2);
-    const bool vec = (W % 4) == 0 && aligned16(f1) && aligned16(f2) && aligned16(pyramid);
-    st = pyr_dtype == DXR_F32
-             ? launch_build_f32(vec, f1, f2, static_cast<float*>(pyramid), g, (int)B, algo, stream)
-             : launch_build_f32(vec, f1, f2, static_cast<uint16_t*>(pyramid), g, (int)B, algo,
-                                stream);
-  } else {
-    const uint16_t* f1 = static_cast<const uint16_t*>(fmap1);
-    const uint16_t* f2 = static_cast<const uint16_t*>(fmap2);
-    const bool vec = (W % 4) == 0 && ((uintptr_t)f1 % 8) == 0 && ((uintptr_t)f2 % 8) == 0 &&
-                     aligned16(pyramid) && D * H * W < (1LL << 30);
-    st = pyr_dtype == DXR_F32
-             ? launch_build_bf16(vec, f1, f2, static_cast<float*>(pyramid), g, (int)B, stream)
-             : launch_build_bf16(vec, f1, f2, static_cast<uint16_t*>(pyramid), g, (int)B, stream);
-  }
-  if (st != DXR_OK) return st;
+  if (st != DXR_OK || !plan.pool_extra) return st;
   return pool_extra_levels(static_cast<float*>(pyramid), L, B, H, W, stream);
 }
 }  // namespace
 
 extern "C" int64_t dxr_build_workspace_bytes(int in_dtype, int64_t B, int64_t D, int64_t H,
                                              int64_t W) {
-  if (B < 0 || D < 1 || H < 1 || W < 1 || H * W > (1LL << 30)) return -1;
-  if (in_dtype == DXR_BF16 || in_dtype == DXR_F16)   // the 16-bit pack pass of NCHW fmaps
-    return D % 32 == 0 ? bf16_pack_bytes(B, D, H, W) : 0;
-  if (in_dtype != DXR_F32 || D % 16 != 0) return 0;
-  return dma_workspace_bytes(B, D, H, W);
+  return dxr::build_workspace_bytes(in_dtype, B, D, H, W);
 }
 
 extern "C" int dxr_corr_pyramid_build_ws(const void* fmap1, const void* fmap2, int in_dtype,
@@ -2639,44 +2531,24 @@ extern "C" int dxr_corr_volume(const void* fmap1, const void* fmap2, int in_dtyp
                                hipStream_t stream) {
   dxr::Levels L;
   if (!dxr::make_levels(B, H, W, 1, &L)) return DXR_EINVAL;
-  const int chk = check_build_args(fmap1, fmap2, in_dtype, B, D, divisor, out, DXR_F32);
-  if (chk != PROCEED) return chk;
+  const int chk = dxr::check_build_args(in_dtype, B, D, divisor, DXR_F32);
+  if (chk != DXR_OK || B == 0) return chk;
+  if (!fmap1 || !fmap2 || !out) return DXR_EINVAL;
   if (in_dtype != DXR_F32) return DXR_EUNSUPPORTED;
+  if (!dxr::grid_rows_ok(H, W)) return DXR_EINVAL;
   const BuildGeom g = make_geom(D, H, W, divisor, L);
   const float* f1 = static_cast<const float*>(fmap1);
   const float* f2 = static_cast<const float*>(fmap2);
-  const bool vec = (W % 4) == 0 && aligned16(f1) && aligned16(f2) && aligned16(out);
+  const bool vec = (W % 4) == 0 && ((uintptr_t)f1 | (uintptr_t)f2 | (uintptr_t)out) % 16 == 0;
   return launch_f32<false>(vec, f1, f2, out, g, (int)B, stream);
 }
 
-extern "C" int dxr_pyramid_unpack(const void* pyramid, int pyr_dtype, int64_t B, int64_t H,
-                                  int64_t W, int num_levels, int level, float* out,
-                                  hipStream_t stream) {
-  dxr::Levels L;
-  if (!dxr::make_levels(B, H, W, num_levels, &L) || level < 0 || level >= num_levels)
-    return DXR_EINVAL;
-  if (pyr_dtype != DXR_F32 && pyr_dtype != DXR_BF16 && pyr_dtype != DXR_PYR_F16) return DXR_EINVAL;
-  if (B == 0) return DXR_OK;
-  if (!pyramid || !out) return DXR_EINVAL;
-  const long long total = B * H * W * (long long)L.h[level] * L.w[level];
-  if (pyr_dtype == DXR_PYR_F16)
-    hipLaunchKernelGGL((repack_kernel<true, _Float16>), dim3(grid_for(total)), dim3(256), 0,
-                       stream, const_cast<_Float16*>(static_cast<const _Float16*>(pyramid)), out,
-                       L.lay[level], (int)B, (int)(H * W));
-  else if (pyr_dtype == DXR_F32)
-    hipLaunchKernelGGL((repack_kernel<true, float>), dim3(grid_for(total)), dim3(256), 0, stream,
-                       const_cast<float*>(static_cast<const float*>(pyramid)), out, L.lay[level],
-                       (int)B, (int)(H * W));
-  else
-    hipLaunchKernelGGL((repack_kernel<true, uint16_t>), dim3(grid_for(total)), dim3(256), 0,
-                       stream, const_cast<uint16_t*>(static_cast<const uint16_t*>(pyramid)), out,
-                       L.lay[level], (int)B, (int)(H * W));
-  return dxr::launch_status();
-}
-
-extern "C" int dxr_pyramid_pack(const float* level_data, int64_t B, int64_t H, int64_t W,
-                                int num_levels, int level, void* pyramid, int pyr_dtype,
-                                hipStream_t stream) {
+namespace {
+// dxr_pyramid_unpack (UNPACK) / dxr_pyramid_pack: one level between the paged
+// pyramid and the reference layout.
+template <bool UNPACK>
+int repack_level(void* pyramid, int pyr_dtype, float* level_data, int64_t B, int64_t H, int64_t W,
+                 int num_levels, int level, hipStream_t stream) {
   dxr::Levels L;
   if (!dxr::make_levels(B, H, W, num_levels, &L) || level < 0 || level >= num_levels)
     return DXR_EINVAL;
@@ -2684,19 +2556,27 @@ extern "C" int dxr_pyramid_pack(const float* level_data, int64_t B, int64_t H, i
   if (B == 0) return DXR_OK;
   if (!pyramid || !level_data) return DXR_EINVAL;
   const long long total = B * H * W * (long long)L.h[level] * L.w[level];
-  float* src = const_cast<float*>(level_data);
-  if (pyr_dtype == DXR_PYR_F16)
-    hipLaunchKernelGGL((repack_kernel<false, _Float16>), dim3(grid_for(total)), dim3(256), 0,
-                       stream, static_cast<_Float16*>(pyramid), src, L.lay[level], (int)B,
-                       (int)(H * W));
-  else if (pyr_dtype == DXR_F32)
-    hipLaunchKernelGGL((repack_kernel<false, float>), dim3(grid_for(total)), dim3(256), 0, stream,
-                       static_cast<float*>(pyramid), src, L.lay[level], (int)B, (int)(H * W));
-  else
-    hipLaunchKernelGGL((repack_kernel<false, uint16_t>), dim3(grid_for(total)), dim3(256), 0,
-                       stream, static_cast<uint16_t*>(pyramid), src, L.lay[level], (int)B,
-                       (int)(H * W));
-  return dxr::launch_status();
+  return with_cells(pyr_dtype, pyramid, [&](auto* p) {
+    using PT = std::remove_pointer_t<decltype(p)>;
+    hipLaunchKernelGGL((repack_kernel<UNPACK, PT>), dim3(grid_for(total)), dim3(256), 0, stream, p,
+                       level_data, L.lay[level], (int)B, (int)(H * W));
+    return dxr::launch_status();
+  });
+}
+}  // namespace
+
+extern "C" int dxr_pyramid_unpack(const void* pyramid, int pyr_dtype, int64_t B, int64_t H,
+                                  int64_t W, int num_levels, int level, float* out,
+                                  hipStream_t stream) {
+  return repack_level<true>(const_cast<void*>(pyramid), pyr_dtype, out, B, H, W, num_levels, level,
+                            stream);
+}
+
+extern "C" int dxr_pyramid_pack(const float* level_data, int64_t B, int64_t H, int64_t W,
+                                int num_levels, int level, void* pyramid, int pyr_dtype,
+                                hipStream_t stream) {
+  return repack_level<false>(pyramid, pyr_dtype, const_cast<float*>(level_data), B, H, W,
+                             num_levels, level, stream);
 }
 
 extern "C" int dxr_pyramid_backward(const void* grad_pyramid, int grad_dtype, int64_t B,

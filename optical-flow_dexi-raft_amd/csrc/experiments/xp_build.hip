@@ -1120,7 +1120,7 @@ extern "C" int dxr_xp_build_strip(const void* f1, const void* f2, int in_dtype, 
   BuildGeom g = make_geom(D, H, W, std::sqrt((float)D), L);
   g.strip = strip;
   if (in_dtype == DXR_F32)
-    return launch_dma<float, false>(static_cast<const float*>(f1), static_cast<const float*>(f2),
+    return launch_dma<false>(static_cast<const float*>(f1), static_cast<const float*>(f2),
                                     static_cast<float*>(pyr), g, (int)B, ws, stream);
   return launch_dma_bf16_nhwc(static_cast<const uint16_t*>(f1), static_cast<const uint16_t*>(f2),
                               static_cast<uint16_t*>(pyr), g, (int)B, stream);
@@ -1154,7 +1154,7 @@ extern "C" int dxr_xp_build_tail(const void* f1, const void* f2, int in_dtype, i
   if (!dxr::make_levels(B, H, W, 4, &L) || tail < 0) return DXR_EINVAL;
   const BuildGeom g = make_geom(D, H, W, std::sqrt((float)D), L);
   if (in_dtype == DXR_F32)
-    return launch_dma<float, false>(static_cast<const float*>(f1), static_cast<const float*>(f2),
+    return launch_dma<false>(static_cast<const float*>(f1), static_cast<const float*>(f2),
                                     static_cast<float*>(pyr), g, (int)B, ws, stream, tail);
   if (fmap_layout == DXR_NHWC)
     return launch_dma_bf16_nhwc(static_cast<const uint16_t*>(f1), static_cast<const uint16_t*>(f2),

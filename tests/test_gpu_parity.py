@@ -1149,9 +1149,11 @@ def test_backward_only_flows_to_fmaps_that_require_grad(dx):
 
 
 # Every build kernel the library can run, by the request that selects it
-# (include/dexiraft_corr.h, "Kernels by request"): the kernel's name is the
-# test id.  Each runs through the C-ABI and is checked against the float64
-# oracle at the dtype's tolerance (f32 1e-4 of max per level, bf16 1e-2).
+# (include/dexiraft_corr.h, "Kernels by request"): the test id names the kernel
+# that request reaches — tests/test_build_plan.py checks which kernel it is, on
+# a CPU, against the planner (csrc/build_plan.h).  Each runs through the C-ABI
+# and is checked against the float64 oracle at the dtype's tolerance (f32 1e-4
+# of max per level, bf16 1e-2).
 _BUILD_PATHS = [
     # id, in dtype, layout, workspace, algo, (B, D, H, W)
     ("split_pairs_kernel+corr_build_dma_kernel", "f32", "nchw", True, "auto", (1, 64, 23, 31)),
