@@ -210,6 +210,16 @@ def corr_lookup(pyramid: list[np.ndarray], coords: np.ndarray, radius: int) -> n
     return np.ascontiguousarray(out.transpose(0, 3, 1, 2))
 
 
+def _cell_index(v0: np.ndarray) -> np.ndarray:
+    """floor(coordinate) as int64.  NaN, +-inf and |v| >= 2^62 have no int64 value
+    (the cast warns and its result depends on the platform): they get -2^62, a
+    cell off every level, so such a query fails the bounds test of
+    correlation_kernel.cu:80 / :194 at every cell whatever the platform."""
+    with np.errstate(invalid="ignore"):
+        ok = np.abs(v0) < F32(2.0 ** 62)
+    return np.where(ok, v0, F32(-2.0 ** 62)).astype(np.int64)
+
+
 def alt_corr_forward(fmap1: np.ndarray, fmap2: np.ndarray, coords: np.ndarray, radius: int,
                      dtype=np.float64) -> np.ndarray:
     """alt_cuda_corr.forward, alt_cuda_corr/correlation_kernel.cu:18-119 + :260-286.
@@ -231,7 +241,7 @@ def alt_corr_forward(fmap1: np.ndarray, fmap2: np.ndarray, coords: np.ndarray, r
     x, y = c[..., 0], c[..., 1]
     x0, y0 = np.floor(x), np.floor(y)
     dx, dy = (x - x0).astype(dtype), (y - y0).astype(dtype)
-    x0i, y0i = x0.astype(np.int64), y0.astype(np.int64)
+    x0i, y0i = _cell_index(x0), _cell_index(y0)
     bidx = np.arange(B)[:, None, None]
     s = np.zeros((rd + 1, rd + 1) + x.shape, dtype=dtype)
     for iy in range(rd + 1):
@@ -273,7 +283,7 @@ def alt_corr_backward(fmap1: np.ndarray, fmap2: np.ndarray, coords: np.ndarray,
     c = np.asarray(coords, dtype=F32).reshape(B, N, Q, 2)
     x0, y0 = np.floor(c[..., 0]), np.floor(c[..., 1])
     dx, dy = (c[..., 0] - x0).astype(dtype), (c[..., 1] - y0).astype(dtype)
-    x0i, y0i = x0.astype(np.int64), y0.astype(np.int64)
+    x0i, y0i = _cell_index(x0), _cell_index(y0)
     bidx = np.arange(B)[:, None, None]
     f1g = np.zeros((B, Q, C), dtype=dtype)
     f2g = np.zeros((B, H2, W2, C), dtype=dtype)

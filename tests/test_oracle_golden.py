@@ -152,6 +152,64 @@ def test_alt_block_oracle_raises_for_small_fmaps():
         oracle.alt_corr_block(f, f, dg.coords(6, 1, 12, 20), 4, 4)
 
 
+@pytest.mark.parametrize("shape", [(2, 272, 18, 21, 6), (1, 80, 44, 48, 4)])
+def test_alt_block_float32_oracle_within_the_gpu_bound(shape):
+    """The bound of tests/test_gpu_alt_oracle.py, |got - ref| <= 1e-5 M per output
+    with M the oracle of |fmap1|, |fmap2|, is one a plain float32 evaluation
+    meets (so it asks nothing of the kernels that float32 arithmetic cannot
+    give), and an output with M == 0 is exactly 0 in float32 too.  Two of that
+    module's shapes: two 256-channel slabs at r = 6, and the 66-tile map."""
+    B, D, H, W, r = shape
+    f1 = dg.fmap(41, B, D, H, W)
+    f2 = dg.fmap(42, B, D, H, W)
+    c = dg.coords(43, B, H, W, "uniform", 8.0)
+    ref = oracle.alt_corr_block(f1, f2, c, 4, r, np.float64)
+    got = oracle.alt_corr_block(f1, f2, c, 4, r, np.float32)
+    M = oracle.alt_corr_block(np.abs(f1), np.abs(f2), c, 4, r, np.float64)
+    assert got.dtype == np.float32 and np.isfinite(ref).all()
+    pos = M > 0
+    k = (2 * r + 1) ** 2
+    for lvl in range(4):
+        assert pos[:, lvl * k:(lvl + 1) * k].any() and not pos[:, lvl * k:(lvl + 1) * k].all()
+    assert not got[~pos].any() and not ref[~pos].any()
+    ratio = np.abs(got[pos] - ref[pos]) / M[pos]
+    print(f"{shape}: float32 oracle max |err| / M {ratio.max():.3e}, {1 - pos.mean():.0%} zeros")
+    assert ratio.max() <= 1e-5
+
+
+def test_alt_oracle_nonfinite_coordinates_are_off_every_level():
+    """A NaN / +-inf coordinate has no int64 cell: the oracle places it off the
+    level without a cast warning, so the query's outputs are NaN (its weights)
+    and it adds nothing to either gradient; 3e9 and 1e30 are plain off-level
+    queries (exact zeros)."""
+    import warnings
+    B, H1, W1, H2, W2, C, r = 1, 3, 4, 5, 6, 8, 1
+    f1 = dg.normal(21, B * H1 * W1 * C).reshape(B, H1, W1, C)
+    f2 = dg.normal(22, B * H2 * W2 * C).reshape(B, H2, W2, C)
+    c = (dg.uniform(23, B * H1 * W1 * 2).reshape(B, 1, H1, W1, 2) * 6 - 1).astype(np.float32)
+    clean = oracle.alt_corr_forward(f1, f2, c, r)
+    g = dg.normal(24, clean.size).reshape(clean.shape)
+    clean_bw = oracle.alt_corr_backward(f1, f2, c, g, r)
+    bad = {(0, 1): np.nan, (1, 2): np.inf, (2, 0): -np.inf, (2, 3): 3e9, (0, 3): 1e30}
+    cp = c.copy()
+    for k, ((y, x), v) in enumerate(bad.items()):
+        cp[0, 0, y, x, k % 2] = v
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        with np.errstate(invalid="ignore"):     # inf - inf and 0 * NaN are the semantics
+            out = oracle.alt_corr_forward(f1, f2, cp, r)
+            g1, g2, _ = oracle.alt_corr_backward(f1, f2, cp, g, r)
+    touched = np.zeros((H1, W1), dtype=bool)
+    for (y, x), v in bad.items():
+        touched[y, x] = True
+        assert np.isnan(out[0, 0, :, y, x]).all() if not np.isfinite(v) else \
+            not out[0, 0, :, y, x].any()
+        assert not g1[0, y, x].any()
+    assert np.array_equal(out[0, 0][:, ~touched], clean[0, 0][:, ~touched])
+    assert np.array_equal(g1[0][~touched], clean_bw[0][0][~touched])
+    assert np.isfinite(g2).all()
+
+
 def test_large_chairs_checksums():
     """Benchmark-shape pin (C1 Chairs 46x62): regenerated inputs + float32 oracle
     vs the reference's checksums and sampled entries."""
