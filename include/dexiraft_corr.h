@@ -116,6 +116,24 @@ enum dxr_dtype {
 #define DXR_OUT_F16 0x100
 #define DXR_OUT_BF16 0x200
 
+/*
+ * Output layout flag of the same two entry points, or-ed onto pyr_dtype alone or
+ * together with exactly one of the dtype flags above (low byte DXR_F32, DXR_BF16
+ * or DXR_PYR_F16): `out` is channels-last, [B, H, W, C] instead of [B, C, H, W]
+ * (C = num_levels*(2r+1)^2 for dxr_corr_lookup, cout for
+ * dxr_corr_lookup_conv1x1).  Element (b, c, h, w) of the unflagged call lands at
+ * ((b*H + h)*W + w)*C + c and is that call's element with the same dtype flag,
+ * bit for bit (NaN levels, far and non-finite coordinates, float16 overflow to
+ * +-inf included): only the address changes.  `out` needs the element's own
+ * alignment (4 bytes for float32, 2 for the 16-bit types) and no byte outside
+ * the B*H*W*C elements is written.  The flag with both dtype flags, with any
+ * other bit above the low byte, on any other low value (DXR_F16 included) or on
+ * any other entry point is DXR_EINVAL, answered on the host before any launch.
+ * (The fmap layout DXR_NHWC of enum dxr_layout below is an input layout of the
+ * builds and unrelated to this flag.)
+ */
+#define DXR_OUT_NHWC 0x1000
+
 enum dxr_layout {
   DXR_NCHW = 0,         /* fmaps [B, D, H, W] (core/raft.py:139-142)              */
   DXR_NHWC = 1          /* fmaps [B, H, W, D] (channels-last encoders, §8(f) row 4) */
@@ -317,6 +335,9 @@ int dxr_pyramid_pack(const float* level_data, int64_t B, int64_t H, int64_t W,
  * float32 call's, converted round-to-nearest-even in the store (float16: overflow
  * to +-inf, subnormals kept; NaN stays NaN): torch's out.to(dtype) bit for bit.
  * No byte outside the elements is written.
+ * pyr_dtype | DXR_OUT_NHWC (alone or with one dtype flag): `out` is
+ * [B, H, W, num_levels*(2r+1)^2], the same elements bit for bit at
+ * ((b*H + h)*W + w)*C + c (see DXR_OUT_NHWC), all radii and level counts.
  */
 int dxr_corr_lookup(const void* pyramid, int pyr_dtype,
                     int64_t B, int64_t H, int64_t W, int num_levels, int radius,
@@ -383,7 +404,9 @@ int dxr_corr_lookup_backward_multi_bound(const float* const* coords,
  *   out           : [B, cout, H, W] float32; with pyr_dtype | DXR_OUT_F16 or
  *                   | DXR_OUT_BF16 float16 / bfloat16 elements (2-byte aligned),
  *                   as dxr_corr_lookup: the same float32 accumulation, bias and
- *                   ReLU, converted round-to-nearest-even in the store
+ *                   ReLU, converted round-to-nearest-even in the store; with
+ *                   | DXR_OUT_NHWC [B, H, W, cout] (channels-last), the same
+ *                   elements bit for bit
  * Supported: radius 3 or 4, num_levels <= 4, cout a multiple of 32 (<= 4096);
  * other valid requests return DXR_EUNSUPPORTED.
  */

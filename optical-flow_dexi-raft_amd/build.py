@@ -48,9 +48,10 @@ def hipcc() -> str:
 def _sources(experiments: bool = False) -> list[Path]:
     if experiments:   # each experiment includes its product source; capi.hip once
         # (and the lookup's 16-bit instantiations, which xp_lookup's entry points call)
-        # and float16-pyramid instantiations
+        # and float16-pyramid and channels-last instantiations
         return sorted(EXP_DIR.glob("*.hip")) + [CSRC / "capi.hip", CSRC / "corr_lookup_out16.hip",
-                                                CSRC / "corr_lookup_pyr16.hip"]
+                                                CSRC / "corr_lookup_pyr16.hip",
+                                                CSRC / "corr_lookup_nhwc.hip"]
     return sorted(CSRC.glob("*.hip"))
 
 
@@ -72,7 +73,8 @@ def is_stale(lib: Path = LIB_PATH) -> bool:
 # 192 -> 182 us at Sintel, other kernels neutral.
 FILE_FLAGS = {"corr_build.hip": ["-fno-slp-vectorize"], "corr_lookup.hip": ["-fno-slp-vectorize"],
               "corr_lookup_out16.hip": ["-fno-slp-vectorize"],
-              "corr_lookup_pyr16.hip": ["-fno-slp-vectorize"]}
+              "corr_lookup_pyr16.hip": ["-fno-slp-vectorize"],
+              "corr_lookup_nhwc.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src: Path, extra: list[str], out_dir: Path = BUILD_DIR) -> Path:

@@ -256,10 +256,10 @@ class _LookupGrad(torch.autograd.Function):
     """Graph node of CorrBlock.__call__ (differentiable in the pyramid only)."""
 
     @staticmethod
-    def forward(ctx, token, coords, block, out_dtype=None):
+    def forward(ctx, token, coords, block, out_dtype=None, memory_format=None):
         ctx.gs = block._gs
         ctx.save_for_backward(coords)
-        return block._lookup(coords, out_dtype)
+        return block._lookup(coords, out_dtype, memory_format)
 
     @staticmethod
     def backward(ctx, gout):
@@ -273,7 +273,7 @@ class _LookupGrad(torch.autograd.Function):
         # no gradient for the token: autograd still runs the build's backward
         # after every lookup's (it waits on the edge, and materialises one zero)
         # without a fill per lookup and the adds that would sum them
-        return None, None, None, None
+        return None, None, None, None, None
 
 
 class _VolumeGrad(torch.autograd.Function):
@@ -428,6 +428,26 @@ def _out_flag(out_dtype) -> tuple[torch.dtype, int]:
         return torch.bfloat16, nat.DXR_OUT_BF16
     raise ValueError(f"out_dtype must be None or one of {', '.join(map(str, _OUT_DTYPES))}; "
                      f"got {out_dtype!r}")
+
+
+def _layout_flag(memory_format) -> int:
+    """Flag or-ed onto pyr_dtype for a ``memory_format`` argument: None and
+    ``torch.contiguous_format`` keep the NCHW stores (0), ``torch.channels_last``
+    selects the kernels' own channels-last stores (``DXR_OUT_NHWC``); anything
+    else raises ``ValueError``."""
+    if memory_format is None or memory_format is torch.contiguous_format:
+        return 0
+    if memory_format is torch.channels_last:
+        return nat.DXR_OUT_NHWC
+    raise ValueError("memory_format must be None, torch.contiguous_format or "
+                     f"torch.channels_last; got {memory_format!r}")
+
+
+def _empty_out(shape, dtype, device, layout_flag: int) -> torch.Tensor:
+    """The output tensor of a lookup: ``[B, C, H, W]``, channels-last strides
+    when the kernel stores channels-last."""
+    fmt = torch.channels_last if layout_flag else torch.contiguous_format
+    return torch.empty(shape, dtype=dtype, device=device, memory_format=fmt)
 
 
 _PYR_FMAP_DTYPES = (torch.float32, torch.float16)
@@ -679,8 +699,16 @@ class CorrBlock:
             self._ref_pyramid = levels
         return self._ref_pyramid
 
-    def __call__(self, coords, out_dtype=None):
+    def __call__(self, coords, out_dtype=None, *, memory_format=None):
         """The radius-r lookup around ``coords``: ``[B, num_levels*(2r+1)^2, H, W]``.
+
+        ``memory_format``: None or ``torch.contiguous_format`` (the default: a
+        contiguous NCHW tensor, as the reference) or ``torch.channels_last``: the
+        same shape and the same elements bit for bit, in a tensor allocated
+        channels-last that the kernel fills in place (``DXR_OUT_NHWC``) — what a
+        channels-last update block would otherwise produce with a layout copy
+        before ``convc1``.  Anything else raises ``ValueError``.  The backward
+        is unchanged (it reads ``grad_out.contiguous()``).
 
         ``out_dtype``: None or torch.float32 (the default: float32, as the
         reference), torch.float16 or torch.bfloat16 (anything else raises
@@ -693,16 +721,17 @@ class CorrBlock:
         """
         B, D, H, W = self._geom
         _out_flag(out_dtype)
+        _layout_flag(memory_format)
         _require_no_grad(coords, what="coords (the reference detaches them, core/raft.py:170)")
         c = _check_coords(coords, B, H, W, self._device)
         if self._token is not None and torch.is_grad_enabled():
-            return _LookupGrad.apply(self._token, c, self, out_dtype)
-        return self._lookup(c, out_dtype)
+            return _LookupGrad.apply(self._token, c, self, out_dtype, memory_format)
+        return self._lookup(c, out_dtype, memory_format)
 
     # Introspection (inspect.signature, help()) reports the reference's own
     # ``__call__(self, coords)`` (core/corr.py:29): the class is a drop-in and its
     # declared surface is pinned to the reference's (tests/test_api_cpu.py).
-    # ``out_dtype`` is an extension on top of it, optional and documented above;
+    # ``out_dtype`` and ``memory_format`` are extensions on top of it, optional and documented above;
     # callers that never pass it get the reference's behaviour.
     __call__.__signature__ = inspect.Signature([
         inspect.Parameter("self", inspect.Parameter.POSITIONAL_OR_KEYWORD),
@@ -716,12 +745,13 @@ class CorrBlock:
         inspect.Parameter("num_levels", inspect.Parameter.POSITIONAL_OR_KEYWORD, default=4),
         inspect.Parameter("radius", inspect.Parameter.POSITIONAL_OR_KEYWORD, default=4)])
 
-    def _lookup(self, c, out_dtype=None):
+    def _lookup(self, c, out_dtype=None, memory_format=None):
         B, D, H, W = self._geom
         rd = 2 * self.radius + 1
         out_torch, flag = _out_flag(out_dtype)
-        out = torch.empty((B, self.num_levels * rd * rd, H, W), dtype=out_torch,
-                          device=self._device)
+        layout = _layout_flag(memory_format)
+        flag |= layout
+        out = _empty_out((B, self.num_levels * rd * rd, H, W), out_torch, self._device, layout)
         lib = nat.load()
         with _Launch(self._device):
             st = lib.dxr_corr_lookup(self._buf.data_ptr(), self._pyr_dt | flag, B, H, W,
@@ -730,7 +760,8 @@ class CorrBlock:
         nat.check(st, "CorrBlock lookup (dxr_corr_lookup)")
         return out
 
-    def lookup_conv1x1(self, coords, weight, bias=None, relu=True, out_dtype=None):
+    def lookup_conv1x1(self, coords, weight, bias=None, relu=True, out_dtype=None, *,
+                       memory_format=None):
         """Lookup fused with the motion encoder's first 1x1 convolution:
         ``F.relu(F.conv2d(self(coords), weight, bias))`` in one launch
         (``dxr_corr_lookup_conv1x1``).
@@ -742,6 +773,8 @@ class CorrBlock:
         (``out_dtype`` torch.float16 / torch.bfloat16: that dtype, equal to the
         float32 result's ``.to(out_dtype)`` bit for bit — same accumulation, bias
         and ReLU in float32, only the store converts; other values as in
+        ``__call__``).  ``memory_format=torch.channels_last``: the same shape and
+        elements in a channels-last tensor, stored so by the kernel (as
         ``__call__``).
         The samples are bit-identical to ``__call__``'s; the contraction runs in
         f32 class on the matrix cores.  Inference only (raises under grad for
@@ -750,6 +783,8 @@ class CorrBlock:
         """
         B, D, H, W = self._geom
         out_torch, flag = _out_flag(out_dtype)
+        layout = _layout_flag(memory_format)
+        flag |= layout
         _require_no_grad(coords, weight, *(() if bias is None else (bias,)),
                          what="CorrBlock.lookup_conv1x1 (inference fusion)")
         if self._token is not None and torch.is_grad_enabled():
@@ -771,7 +806,7 @@ class CorrBlock:
                 raise RuntimeError(f"bias must be [{cout}], got {tuple(bias.shape)}")
             bias = bias.detach().float().contiguous()
         planes = _packed_weight(weight, self._device)
-        out = torch.empty((B, cout, H, W), dtype=out_torch, device=self._device)
+        out = _empty_out((B, cout, H, W), out_torch, self._device, layout)
         lib = nat.load()
         with _Launch(self._device):
             st = lib.dxr_corr_lookup_conv1x1(self._buf.data_ptr(), self._pyr_dt | flag, B, H, W,
@@ -780,6 +815,14 @@ class CorrBlock:
                                              out.data_ptr(), nat.stream_of(c))
         nat.check(st, "CorrBlock.lookup_conv1x1 (dxr_corr_lookup_conv1x1)")
         return out
+
+    # ``memory_format`` (keyword-only) is an extension in the same way: the
+    # declared surface stays the one ``out_dtype`` introduced.
+    lookup_conv1x1.__signature__ = inspect.Signature(
+        [inspect.Parameter(n, inspect.Parameter.POSITIONAL_OR_KEYWORD, default=d)
+         for n, d in (("self", inspect.Parameter.empty), ("coords", inspect.Parameter.empty),
+                      ("weight", inspect.Parameter.empty), ("bias", None), ("relu", True),
+                      ("out_dtype", None))])
 
     @staticmethod
     def corr(fmap1, fmap2):

@@ -56,7 +56,8 @@ struct LookupGeom {
   int N;          // H * W query pixels per pair
   int levels;
   int cout;       // levels * (2r+1)^2
-  int out_nt = 0; // wide lookup: non-temporal output stores (launch_lookup_r decides)
+  int out_nt = 0; // NCHW lookups: non-temporal output stores (launch_lookup_r decides); the channels-last
+                  // forms take their store policy at compile time and do not read it
   int l0 = 0;     // level of blockIdx.y == 0 (the alternate block's volume lookup: its first coarse level)
   float divisor = 1.f, div_recip = 0.f;   // ALT: the alternate block's division of each output
   LevelAddr lv[8];
@@ -709,6 +710,99 @@ __device__ __forceinline__ void store_out16(OT* p, float r, bool word_row, bool 
   store_out16_one<OT, MODE>(p, h, h | (nb << 16), word_row && has_next);
 }
 
+// ---------------------------------------------------------------------------
+// Channels-last outputs (DXR_OUT_NHWC): out is [B, H, W, C], element (b, c, q)
+// at (b * N + q) * C + c.  Same values, bit for bit; only the address changes.
+// Phase 2 keeps its (query, class) mapping — the conflict-free tap reads of the
+// query-minor cells — and hands each result to LDS (res[qq * KCP + k], odd pitch:
+// a half-wave's 32 queries fall on 32 banks); after a barrier the workgroup
+// writes its QB runs of K consecutive channels with lanes along the channels, so
+// a wave instruction covers 256 consecutive bytes of a run (128 with 16-bit
+// outputs) and continues in the next query's run.
+// LDS: the staging area is QB * KCP floats on top of the NCHW form's.  Where that
+// would lower the workgroups resident per CU (r = 7 / 8 with 16 queries), phase 2
+// runs in PASSES chunks of KC channels through a smaller area: the occupancy is
+// the NCHW form's at every radius (static_assert below).
+// ---------------------------------------------------------------------------
+template <int R, int NT_, int QB_>
+struct NhwcCfg {
+  using Q = QmCfg<R, NT_, QB_>;
+  static constexpr int LDS_CU = 160 * 1024, LDS_GRAN = 512;
+  static constexpr int round_lds(int b) { return (b + LDS_GRAN - 1) / LDS_GRAN * LDS_GRAN; }
+  static constexpr int BASE_B = Q::NCELL * Q::QB * 4 + 2 * Q::RD * Q::XP * 8 + Q::QB * 8;
+  static constexpr int WG_WAVES = 32 / (NT_ / 64);   // 8 waves per SIMD
+  static constexpr int wgs(int bytes) {
+    const int n = LDS_CU / round_lds(bytes);
+    return n < WG_WAVES ? n : WG_WAVES;
+  }
+  static constexpr int kcp(int passes) { return ((Q::K + passes - 1) / passes) | 1; }
+  static constexpr int passes() {
+    for (int p = 1; p < 4; ++p)
+      if (wgs(BASE_B + Q::QB * kcp(p) * 4) >= wgs(BASE_B)) return p;
+    return 4;
+  }
+  static constexpr int PASSES = passes();
+  static constexpr int KC = (Q::K + PASSES - 1) / PASSES;   // channels per pass
+  static constexpr int KCP = KC | 1;                         // odd pitch of a query's results
+  static_assert(wgs(BASE_B + Q::QB * KCP * 4) >= wgs(BASE_B), "occupancy of the NCHW form");
+};
+
+// Store policy of the channels-last forms, a compile-time argument: the product
+// instantiates the one its launchers name (launch_lookup_nhwc_r,
+// launch_lookup_conv1x1_r), the experiments target all of them for the A/B.
+enum { NHWC_WRITE_THROUGH = 0, NHWC_NON_TEMPORAL = 1, NHWC_PLAIN = 2 };
+
+template <int POL, typename T>
+__device__ __forceinline__ void store_policy(T* p, T v) {
+  if constexpr (POL == NHWC_NON_TEMPORAL) __builtin_nontemporal_store(v, p);
+  else if constexpr (POL == NHWC_WRITE_THROUGH) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *p = v;
+}
+
+// a * b and acc + a * b (fused) with the operands in exactly this order (see the
+// channels-last phase 2): round to nearest even, as __fmul_rn / fmaf.
+__device__ __forceinline__ float nhwc_mul(float a, float b) {
+  float d;
+  asm("v_mul_f32_e32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+}
+__device__ __forceinline__ float nhwc_fmac(float acc, float a, float b) {
+  asm("v_fmac_f32_e32 %0, %1, %2" : "+v"(acc) : "v"(a), "v"(b));
+  return acc;
+}
+
+// The workgroup's nq runs of N_ channels (res[qq * KCP + kk]) to ob + qq * C + kk.
+// float32: one element per lane.  16-bit: a lane takes the 4-byte aligned word
+// that holds elements e0 = 2s - p, e0 + 1 of the run, p the parity of the run's
+// first element (runs start at odd elements: K and C are odd multiples, and the
+// base may be 2-byte aligned only); where only one of the two lies in the run —
+// its first or last element — the lane stores that element's 2 bytes alone.
+template <typename OT, int NT_, int KCP, int N_, int POL>
+__device__ __forceinline__ void nhwc_store_runs(const float* res, OT* ob, int nq, int C, int tid) {
+  if constexpr (std::is_same_v<OT, float>) {
+    for (int i = tid; i < nq * N_; i += NT_) {
+      const int qq = i / N_, kk = i - qq * N_;
+      store_policy<POL>(ob + (long long)qq * C + kk, res[qq * KCP + kk]);
+    }
+  } else {
+    constexpr int NS = N_ / 2 + 1;   // word slots per run, either parity
+    const int bpar = out16_base_parity(ob);
+    for (int i = tid; i < nq * NS; i += NT_) {
+      const int qq = i / NS, s = i - qq * NS;
+      const int par = (bpar + qq * C) & 1;
+      const int e0 = 2 * s - par, e1 = e0 + 1;
+      const bool in0 = e0 >= 0 && e0 < N_, in1 = e1 < N_;   // e1 >= 0 always
+      if (!in0 && !in1) continue;
+      const float* rq = res + qq * KCP;
+      const uint32_t h0 = out16_bits<OT>(rq[in0 ? e0 : e1]), h1 = out16_bits<OT>(rq[in1 ? e1 : e0]);
+      OT* po = ob + (long long)qq * C;
+      if (in0 && in1) store_policy<POL>(reinterpret_cast<uint32_t*>(po + e0), h0 | (h1 << 16));
+      else if (in0) store_policy<POL>(reinterpret_cast<uint16_t*>(po + e0), (uint16_t)h0);
+      else store_policy<POL>(reinterpret_cast<uint16_t*>(po + e1), (uint16_t)h1);
+    }
+  }
+}
+
 // XA: timing ablations for the experiments target (0 in the product): bit 0 skips
 // the window gathers, bit 1 the output stores (only values equal to 12345 are
 // stored), bit 2 returns after phase 0.
@@ -718,12 +812,14 @@ __device__ __forceinline__ void store_out16(OT* p, float r, bool word_row, bool 
 // weighted by the fractions of c / 2^l and combined in correlation_kernel.cu's
 // order (as alt_corr_mfma_kernel's last phase), then divided by sqrt(D).
 // OT: output element type (float; _Float16 / __bf16: the 16-bit stores above).
+// NHWC: channels-last output (above), stored with policy POL (g.out_nt is not read).
 template <int R, typename PT, int NT_ = 512, int QB_ = 32, int UNR = 1, bool BUF = false, int XA = 0,
-          bool ALT = false, typename OT = float>
+          bool ALT = false, typename OT = float, bool NHWC = false, int POL = NHWC_NON_TEMPORAL>
 __global__ __launch_bounds__(NT_) void corr_lookup_qm_kernel(
     const PT* __restrict__ pyr, const float* __restrict__ coords, OT* __restrict__ out,
     LookupGeom g) {
   static_assert(std::is_same_v<OT, float> || (!ALT && XA == 0), "16-bit outputs: the product lookup only");
+  static_assert(!NHWC || (!ALT && XA == 0), "channels-last outputs: the product lookup only");
   using Q = QmCfg<R, NT_, QB_>;
   constexpr int RD = Q::RD, K = Q::K, QB = Q::QB, RSC = Q::RSC;
   __shared__ __attribute__((aligned(16))) float cells[Q::NCELL * QB];
@@ -764,6 +860,57 @@ __global__ __launch_bounds__(NT_) void corr_lookup_qm_kernel(
   }
   __syncthreads();
 
+  if constexpr (NHWC) {
+    using T = NhwcCfg<R, NT_, QB_>;
+    static_assert(T::PASSES <= 4, "passes below");
+    __shared__ float res[QB * T::KCP];
+    const int qq = tid % QB, cls = tid / QB;
+    const int nq = min(QB, g.N - q0);   // live queries (>= 1)
+    const float* cq = cells + qq;
+    OT* ob = out + ((long long)b * g.N + q0) * g.cout + (long long)l * K;
+    auto pass = [&](auto pc) {
+      constexpr int P = decltype(pc)::value;
+      if constexpr (P < T::PASSES) {
+        constexpr int k0 = P * T::KC, k1 = k0 + T::KC < K ? k0 + T::KC : K;
+        if (P > 0) __syncthreads();   // the previous pass's stores have read res
+        if (qq < nq) {
+          for (int k = k0 + cls; k < k1; k += Q::NCLS) {
+            const int ox = k / RD, oy = k - ox * RD;
+            const float2 xd = xs[ox * Q::XP + qq], yd = ys[oy * Q::XP + qq];
+            const float* p = cq + __float_as_int(yd.x) + __float_as_int(xd.x);
+            const float v00 = p[0], v01 = p[QB], v10 = p[RSC * QB], v11 = p[RSC * QB + QB];
+            const float gx = __fsub_rn(1.f, xd.y), gy = __fsub_rn(1.f, yd.y);
+            // The NCHW form's sums with its operand order pinned (nhwc_mul /
+            // nhwc_fmac): a non-finite coordinate makes fx = +NaN and gx = 1 - fx
+            // = -NaN, and which of two NaN operands an instruction returns depends
+            // on their order, which the compiler is otherwise free to choose per
+            // instantiation.  The order is the one the compiler gives the NCHW
+            // kernels today (x factor first, the cell first in the first product).
+            // That is an observation, not a construction: the NCHW sums are plain
+            // C++ and stay so, and the equality of NaN bits rests on
+            // tests/test_gpu_nhwc_out.py, which compares every radius 0-8 in both
+            // workgroup shapes, every cell and output type, with non-finite
+            // coordinates and a NaN level; a compiler that reorders an NCHW
+            // instantiation fails those tests.
+            const float nw = nhwc_mul(gx, gy), ne = nhwc_mul(xd.y, gy);
+            const float sw = nhwc_mul(gx, yd.y), se = nhwc_mul(xd.y, yd.y);
+            float r = nhwc_mul(v00, nw);
+            r = nhwc_fmac(r, ne, v01);
+            r = nhwc_fmac(r, sw, v10);
+            r = nhwc_fmac(r, se, v11);
+            res[qq * T::KCP + (k - k0)] = r;
+          }
+        }
+        __syncthreads();
+        nhwc_store_runs<OT, NT_, T::KCP, k1 - k0, POL>(res, ob + k0, nq, g.cout, tid);
+      }
+    };
+    pass(std::integral_constant<int, 0>{});
+    pass(std::integral_constant<int, 1>{});
+    pass(std::integral_constant<int, 2>{});
+    pass(std::integral_constant<int, 3>{});
+    return;
+  }
   const int qq = tid % QB, cls = tid / QB;
   if (q0 + qq >= g.N) return;
   const float* cq = cells + qq;
@@ -1133,6 +1280,18 @@ int launch_lookup_wide_r(const PT* pyr, const float* coords, float* out, const L
   return dxr::launch_status();
 }
 
+// The product's workgroup shape (launch_lookup_wide_r's rule, above): true = the one-round 256 x 16
+// shape, false = 512 x 32 (512 x 16 for r > 4).  Shared by the NCHW and the
+// channels-last launchers.
+template <int R, typename PT>
+bool lookup_one_round(const LookupGeom& g, int B) {
+  using W = WideCfg<R>;
+  const long long wg32 = (long long)((g.N + W::QB - 1) / W::QB) * g.levels * B;
+  const double pyr_bytes = (double)B * g.lv[0].qt * (double)g.lv[0].qstride * sizeof(PT) * (4.0 / 3.0);
+  const bool big_misaligned = g.N % 32 != 0 && pyr_bytes >= 128.0 * (1 << 20);
+  return R <= 4 && wg32 <= 1024 && !big_misaligned;
+}
+
 // The product lookup (round 6): the query-minor kernel with the round-5 shape
 // and output policy below (launch_lookup_wide_r).  One-round grids (256 x 16)
 // load their window vectors with plain global loads, multi-round grids (512 x
@@ -1152,10 +1311,7 @@ int launch_lookup_r(const PT* pyr, const float* coords, OT* out, const LookupGeo
                        hipStream_t stream) {
   using W = WideCfg<R>;
   LookupGeom g = g0;
-  const long long wg32 = (long long)((g.N + W::QB - 1) / W::QB) * g.levels * B;
-  const double pyr_bytes = (double)B * g.lv[0].qt * (double)g.lv[0].qstride * sizeof(PT) * (4.0 / 3.0);
-  const bool big_misaligned = g.N % 32 != 0 && pyr_bytes >= 128.0 * (1 << 20);
-  if (R <= 4 && wg32 <= 1024 && !big_misaligned) {
+  if (lookup_one_round<R, PT>(g, B)) {
     g.out_nt = g.N % 32 == 0 ? 1 : 0;
     const dim3 grid((unsigned)((g.N + ONE_QB - 1) / ONE_QB), (unsigned)g.levels, (unsigned)B);
     hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 256, ONE_QB, UNR, ONE_BUF, XA, false, OT>), grid,
@@ -1170,9 +1326,54 @@ int launch_lookup_r(const PT* pyr, const float* coords, OT* out, const LookupGeo
   return dxr::launch_status();
 }
 
-template <typename PT, typename OT>
+// The channels-last lookup (DXR_OUT_NHWC): launch_lookup_r's two workgroup
+// shapes, chosen by the same rule, with the stores along channels.
+// Output store policy: the NCHW rule above was derived for whole or half lines
+// along queries and does not carry over — here a wave instruction covers 256
+// consecutive bytes (128 with 16-bit outputs) of a query's run of K channels,
+// which starts wherever l * K elements into the query's row falls.
+// Rule (same-process A/B in the step, scripts/ab_nhwc_out.py, profiles/r11/nhwc_out/):
+// non-temporal stores in both shapes.  Per step (build + 12 lookups), non-temporal /
+// write-through / plain: Sintel B=1 213.4 / 231.2 / 229.1 us, Sintel B=8 1,357 /
+// 1,431 / 1,398, KITTI B=8 bf16 939 / 1,019 / 1,018, Sintel B=8 float16 outputs
+// 1,328 / 1,383 / 1,354 (A/A spread 1-8 us): as in the NCHW form, outputs that
+// leave the caches keep the pyramid lines of the next lookups resident.
+// POL: the experiments target instantiates the other policies for that A/B.
+template <int R, typename PT, typename OT, int POL = NHWC_NON_TEMPORAL>
+int launch_lookup_nhwc_r(const PT* pyr, const float* coords, OT* out, const LookupGeom& g, int B,
+                         hipStream_t stream) {
+  using W = WideCfg<R>;
+  if constexpr (R <= 4) {   // the one-round shape exists for these radii only
+    if (lookup_one_round<R, PT>(g, B)) {
+      const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)g.levels, (unsigned)B);
+      hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 256, 16, 1, false, 0, false, OT, true, POL>), grid,
+                         dim3(256), 0, stream, pyr, coords, out, g);
+      return dxr::launch_status();
+    }
+  }
+  const dim3 grid((unsigned)((g.N + W::QB - 1) / W::QB), (unsigned)g.levels, (unsigned)B);
+  hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 512, W::QB, 1, true, 0, false, OT, true, POL>), grid,
+                     dim3(512), 0, stream, pyr, coords, out, g);
+  return dxr::launch_status();
+}
+
+template <typename PT, typename OT, bool NHWC = false>
 int launch_lookup(const PT* pyr, const float* coords, OT* out, const LookupGeom& g, int B,
                   int radius, hipStream_t stream) {
+  if constexpr (NHWC) {
+    switch (radius) {
+      case 0: return launch_lookup_nhwc_r<0, PT>(pyr, coords, out, g, B, stream);
+      case 1: return launch_lookup_nhwc_r<1, PT>(pyr, coords, out, g, B, stream);
+      case 2: return launch_lookup_nhwc_r<2, PT>(pyr, coords, out, g, B, stream);
+      case 3: return launch_lookup_nhwc_r<3, PT>(pyr, coords, out, g, B, stream);
+      case 4: return launch_lookup_nhwc_r<4, PT>(pyr, coords, out, g, B, stream);
+      case 5: return launch_lookup_nhwc_r<5, PT>(pyr, coords, out, g, B, stream);
+      case 6: return launch_lookup_nhwc_r<6, PT>(pyr, coords, out, g, B, stream);
+      case 7: return launch_lookup_nhwc_r<7, PT>(pyr, coords, out, g, B, stream);
+      case 8: return launch_lookup_nhwc_r<8, PT>(pyr, coords, out, g, B, stream);
+      default: return DXR_EUNSUPPORTED;
+    }
+  } else {
   switch (radius) {
     case 0: return launch_lookup_r<0, PT>(pyr, coords, out, g, B, stream);
     case 1: return launch_lookup_r<1, PT>(pyr, coords, out, g, B, stream);
@@ -1184,6 +1385,7 @@ int launch_lookup(const PT* pyr, const float* coords, OT* out, const LookupGeom&
     case 7: return launch_lookup_r<7, PT>(pyr, coords, out, g, B, stream);
     case 8: return launch_lookup_r<8, PT>(pyr, coords, out, g, B, stream);
     default: return DXR_EUNSUPPORTED;
+  }
   }
 }
 
@@ -1291,7 +1493,13 @@ __global__ __launch_bounds__(256) void conv1x1_pack_weight_kernel(const float* _
 // ---------------------------------------------------------------------------
 typedef _Float16 mh8 __attribute__((ext_vector_type(8)));
 
-template <int R, typename PT, int NT = 512, int PF = 4, typename OT = float>
+// NHWC (DXR_OUT_NHWC): out is [B, H, W, Cout].  A lane's four consecutive output
+// rows (r & 3) of one query are 16 (float32) / 8 (16-bit) contiguous bytes of that
+// query's row there and go out as one vector store, aligned as the element is;
+// POL = NHWC_NON_TEMPORAL makes them non-temporal (else plain).  Bias, ReLU and the rounding are the NCHW
+// form's.
+template <int R, typename PT, int NT = 512, int PF = 4, typename OT = float, bool NHWC = false,
+          int POL = NHWC_PLAIN>
 __global__ __launch_bounds__(NT, 4) void corr_lookup_conv1x1_h2_kernel(
     const PT* __restrict__ pyr, const float* __restrict__ coords, const float4* __restrict__ wpk,
     const float* __restrict__ bias, OT* __restrict__ out, LookupGeom g, int cout, int relu) {
@@ -1468,6 +1676,32 @@ __global__ __launch_bounds__(NT, 4) void corr_lookup_conv1x1_h2_kernel(
           for (int r = 0; r < 16; ++r) bad |= !(__builtin_fabsf(acc[r]) <= 3.40282347e38f);
           if (bad) nonfinite = 1;
         }
+        if constexpr (NHWC) {
+          OT* oq = out + ((long long)b * g.N + q) * cout + ob * 32 + 4 * kh;
+#pragma unroll
+          for (int r4 = 0; r4 < 4; ++r4) {
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              v[e] = acc[4 * r4 + e] + (bias ? bias[ob * 32 + e + 8 * r4 + 4 * kh] : 0.f);
+              if (relu && v[e] < 0.f) v[e] = 0.f;
+            }
+            if constexpr (std::is_same_v<OT, float>) {
+              typedef float f4e __attribute__((ext_vector_type(4), aligned(4)));
+              const f4e w = {v[0], v[1], v[2], v[3]};
+              f4e* po = reinterpret_cast<f4e*>(oq + 8 * r4);
+              if constexpr (POL == NHWC_NON_TEMPORAL) __builtin_nontemporal_store(w, po);
+              else *po = w;
+            } else {
+              typedef uint32_t u2e __attribute__((ext_vector_type(2), aligned(2)));
+              const u2e w = {out16_bits<OT>(v[0]) | (out16_bits<OT>(v[1]) << 16),
+                             out16_bits<OT>(v[2]) | (out16_bits<OT>(v[3]) << 16)};
+              u2e* po = reinterpret_cast<u2e*>(oq + 8 * r4);
+              if constexpr (POL == NHWC_NON_TEMPORAL) __builtin_nontemporal_store(w, po);
+              else *po = w;
+            }
+          }
+        } else {
         OT* ob_out = out + (long long)b * cout * g.N + q;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -1483,6 +1717,7 @@ __global__ __launch_bounds__(NT, 4) void corr_lookup_conv1x1_h2_kernel(
             store_out16<OT, 0>(ob_out + (long long)orow * g.N, v, word_row, j & 1, q + 1 < g.N);
           }
         }
+        }
       }
     }
   };
@@ -1491,7 +1726,11 @@ __global__ __launch_bounds__(NT, 4) void corr_lookup_conv1x1_h2_kernel(
   if (nonfinite) gemm(std::integral_constant<bool, false>{});   // workgroup-uniform
 }
 
-template <int R, typename PT, typename OT>
+// NHWC: plain vector stores, as the NCHW form's (12 calls at Sintel B=1 / B=2: plain
+// 260.6 / 374.1 us, non-temporal 286.1 / 376.9;
+// profiles/r11/nhwc_out/conv_*.json);
+// POL: the experiments target instantiates non-temporal too.
+template <int R, typename PT, typename OT, bool NHWC = false, int POL = NHWC_PLAIN>
 int launch_lookup_conv1x1_r(const PT* pyr, const float* coords, const float4* wpl,
                             const float* bias, OT* out, const LookupGeom& g, int B, int cout,
                             int relu, hipStream_t stream) {
@@ -1503,21 +1742,21 @@ int launch_lookup_conv1x1_r(const PT* pyr, const float* coords, const float4* wp
   // ~76 KB LDS and 128 VGPRs, two workgroups per CU (Sintel B=2: 35 vs 47 us,
   // KITTI-shape B=8: 136 vs 190 us; r01 kernel 52 / 214 us).
   if ((long long)grid.x * grid.y <= 256)
-    hipLaunchKernelGGL((corr_lookup_conv1x1_h2_kernel<R, PT, 1024, 4, OT>), grid, dim3(1024), 0,
+    hipLaunchKernelGGL((corr_lookup_conv1x1_h2_kernel<R, PT, 1024, 4, OT, NHWC, POL>), grid, dim3(1024), 0,
                        stream, pyr, coords, wpl, bias, out, g, cout, relu);
   else
-    hipLaunchKernelGGL((corr_lookup_conv1x1_h2_kernel<R, PT, 512, 4, OT>), grid, dim3(512), 0, stream,
+    hipLaunchKernelGGL((corr_lookup_conv1x1_h2_kernel<R, PT, 512, 4, OT, NHWC, POL>), grid, dim3(512), 0, stream,
                        pyr, coords, wpl, bias, out, g, cout, relu);
   return dxr::launch_status();
 }
 
-template <typename PT, typename OT>
+template <typename PT, typename OT, bool NHWC = false>
 int launch_lookup_conv1x1(const PT* pyr, const float* coords, const float4* wpl, const float* bias,
                           OT* out, const LookupGeom& g, int B, int radius, int cout, int relu,
                           hipStream_t stream) {
   switch (radius) {
-    case 3: return launch_lookup_conv1x1_r<3, PT, OT>(pyr, coords, wpl, bias, out, g, B, cout, relu, stream);
-    case 4: return launch_lookup_conv1x1_r<4, PT, OT>(pyr, coords, wpl, bias, out, g, B, cout, relu, stream);
+    case 3: return launch_lookup_conv1x1_r<3, PT, OT, NHWC>(pyr, coords, wpl, bias, out, g, B, cout, relu, stream);
+    case 4: return launch_lookup_conv1x1_r<4, PT, OT, NHWC>(pyr, coords, wpl, bias, out, g, B, cout, relu, stream);
     default: return DXR_EUNSUPPORTED;
   }
 }
@@ -1527,7 +1766,9 @@ int launch_lookup_conv1x1(const PT* pyr, const float* coords, const float4* wpl,
 // _Float16 / __bf16 are instantiated in corr_lookup_out16.hip only — co-compiled
 // with them, several float32-output kernels were allocated two more VGPRs
 // (DESIGN.md §3.11), and the float32 path is to stay the code it was.
-template <typename OT>
+// NHWC (channels-last `out`): instantiated in corr_lookup_nhwc.hip only, for
+// every cell and output type.
+template <typename OT, bool NHWC = false>
 int corr_lookup_impl(const void* pyramid, int pyr_dtype, int64_t B, int64_t H, int64_t W,
                      int num_levels, int radius, const float* coords, OT* out,
                      hipStream_t stream) {
@@ -1544,21 +1785,24 @@ int corr_lookup_impl(const void* pyramid, int pyr_dtype, int64_t B, int64_t H, i
   g.levels = num_levels;
   g.cout = num_levels * rd * rd;
   for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
-#ifdef DXR_LOOKUP_PYR16_TU   // float16 cells, and only them (corr_lookup_pyr16.hip)
+#if defined(DXR_LOOKUP_PYR16_TU) || defined(DXR_LOOKUP_NHWC_TU)
+  // float16 cells: corr_lookup_pyr16.hip (and only them), corr_lookup_nhwc.hip
   if (pyr_dtype == DXR_PYR_F16)
-    return launch_lookup(static_cast<const _Float16*>(pyramid), coords, out, g, (int)B, radius,
-                         stream);
-#else
+    return launch_lookup<_Float16, OT, NHWC>(static_cast<const _Float16*>(pyramid), coords, out, g,
+                                             (int)B, radius, stream);
+#endif
+#ifndef DXR_LOOKUP_PYR16_TU
   if (pyr_dtype == DXR_F32)
-    return launch_lookup(static_cast<const float*>(pyramid), coords, out, g, (int)B, radius, stream);
+    return launch_lookup<float, OT, NHWC>(static_cast<const float*>(pyramid), coords, out, g, (int)B,
+                                          radius, stream);
   if (pyr_dtype == DXR_BF16)
-    return launch_lookup(static_cast<const uint16_t*>(pyramid), coords, out, g, (int)B, radius,
-                         stream);
+    return launch_lookup<uint16_t, OT, NHWC>(static_cast<const uint16_t*>(pyramid), coords, out, g,
+                                             (int)B, radius, stream);
 #endif
   return DXR_EINVAL;
 }
 
-template <typename OT>
+template <typename OT, bool NHWC = false>
 int corr_lookup_conv1x1_impl(const void* pyramid, int pyr_dtype, int64_t B, int64_t H, int64_t W,
                              int num_levels, int radius, const float* coords,
                              const void* weight_packed, const float* bias, int64_t cout, int relu,
@@ -1578,17 +1822,21 @@ int corr_lookup_conv1x1_impl(const void* pyramid, int pyr_dtype, int64_t B, int6
   g.cout = num_levels * rd * rd;
   for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
   const float4* wpl = static_cast<const float4*>(weight_packed);
-#ifdef DXR_LOOKUP_PYR16_TU
+#if defined(DXR_LOOKUP_PYR16_TU) || defined(DXR_LOOKUP_NHWC_TU)
   if (pyr_dtype == DXR_PYR_F16)
-    return launch_lookup_conv1x1(static_cast<const _Float16*>(pyramid), coords, wpl, bias, out, g,
-                                 (int)B, radius, (int)cout, relu, stream);
-#else
+    return launch_lookup_conv1x1<_Float16, OT, NHWC>(static_cast<const _Float16*>(pyramid), coords,
+                                                     wpl, bias, out, g, (int)B, radius, (int)cout,
+                                                     relu, stream);
+#endif
+#ifndef DXR_LOOKUP_PYR16_TU
   if (pyr_dtype == DXR_F32)
-    return launch_lookup_conv1x1(static_cast<const float*>(pyramid), coords, wpl, bias, out, g,
-                                 (int)B, radius, (int)cout, relu, stream);
+    return launch_lookup_conv1x1<float, OT, NHWC>(static_cast<const float*>(pyramid), coords, wpl,
+                                                  bias, out, g, (int)B, radius, (int)cout, relu,
+                                                  stream);
   if (pyr_dtype == DXR_BF16)
-    return launch_lookup_conv1x1(static_cast<const uint16_t*>(pyramid), coords, wpl, bias, out, g,
-                                 (int)B, radius, (int)cout, relu, stream);
+    return launch_lookup_conv1x1<uint16_t, OT, NHWC>(static_cast<const uint16_t*>(pyramid), coords,
+                                                     wpl, bias, out, g, (int)B, radius, (int)cout,
+                                                     relu, stream);
 #endif
   return DXR_EINVAL;
 }
@@ -1625,6 +1873,38 @@ int dxr::lookup_conv1x1_pyr16(const void* pyramid, int out_flag, int64_t B, int6
                                     stream);
   return corr_lookup_conv1x1_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
                                   weight_packed, bias, cout, relu, static_cast<float*>(out), stream);
+}
+#elif defined(DXR_LOOKUP_NHWC_TU)
+// corr_lookup_nhwc.hip: this file's templates with channels-last outputs (every
+// cell type, every output type), and nothing else of it.
+int dxr::lookup_nhwc(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H,
+                     int64_t W, int num_levels, int radius, const float* coords, void* out,
+                     hipStream_t stream) {
+  if (out_flag == DXR_OUT_F16)
+    return corr_lookup_impl<_Float16, true>(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
+                                            static_cast<_Float16*>(out), stream);
+  if (out_flag == DXR_OUT_BF16)
+    return corr_lookup_impl<__bf16, true>(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
+                                          static_cast<__bf16*>(out), stream);
+  return corr_lookup_impl<float, true>(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
+                                       static_cast<float*>(out), stream);
+}
+
+int dxr::lookup_conv1x1_nhwc(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H,
+                             int64_t W, int num_levels, int radius, const float* coords,
+                             const void* weight_packed, const float* bias, int64_t cout, int relu,
+                             void* out, hipStream_t stream) {
+  if (out_flag == DXR_OUT_F16)
+    return corr_lookup_conv1x1_impl<_Float16, true>(pyramid, pyr_dtype, B, H, W, num_levels, radius,
+                                                    coords, weight_packed, bias, cout, relu,
+                                                    static_cast<_Float16*>(out), stream);
+  if (out_flag == DXR_OUT_BF16)
+    return corr_lookup_conv1x1_impl<__bf16, true>(pyramid, pyr_dtype, B, H, W, num_levels, radius,
+                                                  coords, weight_packed, bias, cout, relu,
+                                                  static_cast<__bf16*>(out), stream);
+  return corr_lookup_conv1x1_impl<float, true>(pyramid, pyr_dtype, B, H, W, num_levels, radius,
+                                               coords, weight_packed, bias, cout, relu,
+                                               static_cast<float*>(out), stream);
 }
 #elif defined(DXR_LOOKUP_OUT16_TU)
 // corr_lookup_out16.hip: this file's templates with the 16-bit output types, and
@@ -1721,21 +2001,25 @@ extern "C" int dxr_alt_volume_lookup(const float* volumes, const float* coords, 
 }
 
 namespace {
-// The output dtype flag of dxr_corr_lookup / dxr_corr_lookup_conv1x1 (DXR_OUT_F16,
-// DXR_OUT_BF16, or-ed onto a DXR_F32 / DXR_BF16 / DXR_PYR_F16 pyr_dtype): splits it off.  False
-// (DXR_EINVAL) for both flags, any other high bit, a flag on another low value,
-// or a flagged `out` that is not 2-byte aligned.  Unflagged values pass through
-// to the callers' own checks.
-bool split_out_dtype(int* pyr_dtype, int* out_flag, const void* out) {
+// The output flags of dxr_corr_lookup / dxr_corr_lookup_conv1x1 (the dtype flags
+// DXR_OUT_F16 / DXR_OUT_BF16 and the layout flag DXR_OUT_NHWC, or-ed onto a DXR_F32 /
+// DXR_BF16 / DXR_PYR_F16 pyr_dtype): splits them off.  False (DXR_EINVAL) for both
+// dtype flags, any other high bit, a flag on another low value, or a `out` with a
+// dtype flag that is not 2-byte aligned.  Unflagged values pass through to the
+// callers' own checks.
+bool split_out_dtype(int* pyr_dtype, int* out_flag, bool* nhwc, const void* out) {
   const int hi = *pyr_dtype & ~0xff;
   *out_flag = 0;
+  *nhwc = false;
   if (hi == 0) return true;
-  if (hi != DXR_OUT_F16 && hi != DXR_OUT_BF16) return false;
+  const int dt = hi & ~DXR_OUT_NHWC;
+  if (dt != 0 && dt != DXR_OUT_F16 && dt != DXR_OUT_BF16) return false;
   const int lo = *pyr_dtype & 0xff;
   if (lo != DXR_F32 && lo != DXR_BF16 && lo != DXR_PYR_F16) return false;
-  if (reinterpret_cast<uintptr_t>(out) & 1) return false;
+  if (dt != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return false;
   *pyr_dtype = lo;
-  *out_flag = hi;
+  *out_flag = dt;
+  *nhwc = (hi & DXR_OUT_NHWC) != 0;
   return true;
 }
 }  // namespace
@@ -1744,7 +2028,11 @@ extern "C" int dxr_corr_lookup(const void* pyramid, int pyr_dtype, int64_t B, in
                                int64_t W, int num_levels, int radius, const float* coords,
                                float* out, hipStream_t stream) {
   int out_flag;
-  if (!split_out_dtype(&pyr_dtype, &out_flag, out)) return DXR_EINVAL;
+  bool nhwc;
+  if (!split_out_dtype(&pyr_dtype, &out_flag, &nhwc, out)) return DXR_EINVAL;
+  if (nhwc)   // channels-last outputs: their own translation unit, every cell and output type
+    return dxr::lookup_nhwc(pyramid, pyr_dtype, out_flag, B, H, W, num_levels, radius, coords, out,
+                            stream);
   if (pyr_dtype == DXR_PYR_F16)   // float16 cells: their own translation unit, every output type
     return dxr::lookup_pyr16(pyramid, out_flag, B, H, W, num_levels, radius, coords, out, stream);
   if (out_flag)
@@ -1878,7 +2166,11 @@ extern "C" int dxr_corr_lookup_conv1x1(const void* pyramid, int pyr_dtype, int64
                                        const void* weight_packed, const float* bias, int64_t cout,
                                        int relu, float* out, hipStream_t stream) {
   int out_flag;
-  if (!split_out_dtype(&pyr_dtype, &out_flag, out)) return DXR_EINVAL;
+  bool nhwc;
+  if (!split_out_dtype(&pyr_dtype, &out_flag, &nhwc, out)) return DXR_EINVAL;
+  if (nhwc)
+    return dxr::lookup_conv1x1_nhwc(pyramid, pyr_dtype, out_flag, B, H, W, num_levels, radius,
+                                    coords, weight_packed, bias, cout, relu, out, stream);
   if (pyr_dtype == DXR_PYR_F16)
     return dxr::lookup_conv1x1_pyr16(pyramid, out_flag, B, H, W, num_levels, radius, coords,
                                      weight_packed, bias, cout, relu, out, stream);

@@ -42,6 +42,18 @@ int lookup_conv1x1_pyr16(const void* pyramid, int out_flag, int64_t B, int64_t H
                          int num_levels, int radius, const float* coords, const void* weight_packed,
                          const float* bias, int64_t cout, int relu, void* out, hipStream_t stream);
 
+// The same two calls with the layout flag DXR_OUT_NHWC (split off and validated by
+// the entry points): `out` is [B, H, W, C]; pyr_dtype DXR_F32 / DXR_BF16 /
+// DXR_PYR_F16; out_flag 0 (float32), DXR_OUT_F16 or DXR_OUT_BF16.  Defined in
+// corr_lookup_nhwc.hip, the only translation unit that instantiates the
+// channels-last forms of the lookup kernels.
+int lookup_nhwc(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H, int64_t W,
+                int num_levels, int radius, const float* coords, void* out, hipStream_t stream);
+int lookup_conv1x1_nhwc(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H,
+                        int64_t W, int num_levels, int radius, const float* coords,
+                        const void* weight_packed, const float* bias, int64_t cout, int relu,
+                        void* out, hipStream_t stream);
+
 // ---------------------------------------------------------------------------
 // Pyramid layout ("paged" correlation volume).
 //

@@ -395,3 +395,51 @@ extern "C" int dxr_xp_lookup(const void* pyramid, int pyr_dtype, int64_t B, int6
   return xp_dispatch(xp, static_cast<const uint16_t*>(pyramid), coords, out, g, (int)B, trace,
                      stream);
 }
+
+// The channels-last lookup (radius 4) / fused lookup + conv with a forced output
+// store policy (0 write-through, 1 non-temporal, 2 plain; the fused call: 1 or 2):
+// the arms of scripts/ab_nhwc_out.py.  out_flag: 0 float32, DXR_OUT_F16 float16.
+// cout == 0: the lookup; else the fused call (weight_packed, bias, relu = 1).
+extern "C" int dxr_xp_lookup_nhwc(const void* pyramid, int pyr_dtype, int out_flag, int64_t B,
+                                  int64_t H, int64_t W, int num_levels, const float* coords,
+                                  const void* weight_packed, const float* bias, int64_t cout,
+                                  void* out, int policy, hipStream_t stream) {
+  dxr::Levels L;
+  if (!dxr::make_levels(B, H, W, num_levels, &L) || num_levels > 4) return DXR_EINVAL;
+  if (out_flag != 0 && out_flag != DXR_OUT_F16) return DXR_EINVAL;
+  LookupGeom g;
+  g.N = (int)(H * W);
+  g.levels = num_levels;
+  g.cout = num_levels * 81;
+  for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
+  auto run = [&](auto* pyr, auto* o) {
+    typedef std::remove_const_t<std::remove_pointer_t<decltype(pyr)>> PT;
+    typedef std::remove_pointer_t<decltype(o)> OT;
+    const float4* wpk = static_cast<const float4*>(weight_packed);
+    if (cout == 0) {
+      switch (policy) {
+        case NHWC_WRITE_THROUGH:
+          return launch_lookup_nhwc_r<4, PT, OT, NHWC_WRITE_THROUGH>(pyr, coords, o, g, (int)B, stream);
+        case NHWC_NON_TEMPORAL:
+          return launch_lookup_nhwc_r<4, PT, OT, NHWC_NON_TEMPORAL>(pyr, coords, o, g, (int)B, stream);
+        case NHWC_PLAIN:
+          return launch_lookup_nhwc_r<4, PT, OT, NHWC_PLAIN>(pyr, coords, o, g, (int)B, stream);
+        default: return (int)DXR_EINVAL;
+      }
+    }
+    if (policy == NHWC_NON_TEMPORAL)
+      return launch_lookup_conv1x1_r<4, PT, OT, true, NHWC_NON_TEMPORAL>(pyr, coords, wpk, bias, o, g, (int)B,
+                                                                         (int)cout, 1, stream);
+    if (policy == NHWC_PLAIN)
+      return launch_lookup_conv1x1_r<4, PT, OT, true, NHWC_PLAIN>(pyr, coords, wpk, bias, o, g, (int)B,
+                                                                  (int)cout, 1, stream);
+    return (int)DXR_EINVAL;
+  };
+  auto by_out = [&](auto* pyr) {
+    if (out_flag) return run(pyr, static_cast<_Float16*>(out));
+    return run(pyr, static_cast<float*>(out));
+  };
+  if (pyr_dtype == DXR_F32) return by_out(static_cast<const float*>(pyramid));
+  if (pyr_dtype == DXR_BF16) return by_out(static_cast<const uint16_t*>(pyramid));
+  return DXR_EINVAL;
+}
