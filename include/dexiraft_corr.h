@@ -106,12 +106,16 @@ enum dxr_dtype {
 };
 
 /*
- * Output dtype flags of dxr_corr_lookup and dxr_corr_lookup_conv1x1 only: or-ed
+ * Output dtype flags of dxr_corr_lookup and dxr_corr_lookup_conv1x1: or-ed
  * onto their pyr_dtype argument (DXR_F32, DXR_BF16 or DXR_PYR_F16), they make the
  * call store `out` as IEEE float16 / bfloat16 elements instead of float32 (same
  * ABI, no new entry point).  Both flags together, any other bit above the low
  * byte, a flag on any other low value (DXR_F16 included) and a flag passed to any
  * other entry point are DXR_EINVAL, answered on the host before any launch.
+ * The alternate block's lookups (dxr_alt_corr_lookup, dxr_alt_corr_lookup_ws,
+ * dxr_alt_corr_lookup_levels_ws, dxr_alt_volume_lookup) have no pyr_dtype and
+ * take the same flags, with the same meaning, on their `radius` argument: see
+ * "Output flags on radius" at dxr_alt_corr_lookup.
  */
 #define DXR_OUT_F16 0x100
 #define DXR_OUT_BF16 0x200
@@ -130,7 +134,8 @@ enum dxr_dtype {
  * other bit above the low byte, on any other low value (DXR_F16 included) or on
  * any other entry point is DXR_EINVAL, answered on the host before any launch.
  * (The fmap layout DXR_NHWC of enum dxr_layout below is an input layout of the
- * builds and unrelated to this flag.)
+ * builds and unrelated to this flag.)  The alternate block's four lookups take it
+ * on `radius` ("Output flags on radius" at dxr_alt_corr_lookup).
  */
 #define DXR_OUT_NHWC 0x1000
 
@@ -541,6 +546,35 @@ int dxr_alt_corr_backward(const float* fmap1, const float* fmap2,
  *                  H_l = floor(H_{l-1}/2)
  *   coords       : [B, 2, H, W] float32 (CorrBlock convention)
  *   out          : [B, num_levels*(2r+1)^2, H, W] float32
+ *
+ * Output flags on radius.  DXR_OUT_F16, DXR_OUT_BF16 and DXR_OUT_NHWC may be
+ * or-ed onto the `radius` argument of dxr_alt_corr_lookup, dxr_alt_corr_lookup_ws,
+ * dxr_alt_corr_lookup_levels_ws and dxr_alt_volume_lookup (not of
+ * dxr_alt_corr_forward / _backward); the low byte is the radius.  Semantics are
+ * dxr_corr_lookup's:
+ *   DXR_OUT_F16 / DXR_OUT_BF16  `out` holds float16 / bfloat16 elements (passed
+ *       through the float* parameter, 2-byte aligned; an odd address is
+ *       DXR_EINVAL): each is the unflagged call's float32 element rounded to
+ *       nearest even in the store (float16 overflows to +-inf, subnormals are
+ *       kept, NaN stays NaN), i.e. out.to(dtype) bit for bit, a NaN's bits
+ *       included (float16 keeps its sign and payload; bfloat16 is 0x7FC0 for
+ *       every NaN, as torch converts);
+ *   DXR_OUT_NHWC (alone or with one dtype flag)  `out` is [B, H, W, C],
+ *       C = num_levels*(2r+1)^2: element (b, c, h, w) of the NCHW call lands at
+ *       ((b*H + h)*W + w)*C + c with the same bits.
+ * No byte outside the call's own elements is written under either flag: a partial
+ * call (_levels_ws with n_levels < num_levels, dxr_alt_volume_lookup from
+ * first_level) writes only its levels' channels of each pixel's run of C, so the
+ * two partial calls fill one tensor when given the same flags.  Both dtype flags
+ * together, or any other bit above the low byte, is DXR_EINVAL, answered on the
+ * host before every other check (the B == 0 return and the pointer checks
+ * included) and before any launch.
+ * Which forms implement the flags: the MFMA forms of the three on-the-fly calls
+ * (C % 16 == 0, C <= 256, 16-byte aligned operands; tile order, ordered and
+ * _levels_ws, radius 0..6) and dxr_alt_volume_lookup (radius 0..8) implement
+ * every combination natively.  The per-query VALU forms (any other C, or
+ * misaligned operands) decline a flagged request with DXR_EUNSUPPORTED and
+ * launch nothing; the caller runs the unflagged call and converts.
  */
 int dxr_alt_corr_lookup(const float* fmap1, const float* const* fmap2_levels,
                         const float* coords, float* out,
@@ -608,7 +642,9 @@ int dxr_alt_corr_lookup_levels_ws(const float* fmap1, const float* const* fmap2_
  *                           arithmetic (origin floor(c / 2^l) - r, bilinear
  *                           weights of the fraction, :92-114's order, divided
  *                           by divisor) into those levels' channels of `out`
- *                           ([B, num_levels*(2r+1)^2, H, W]); r <= 8.
+ *                           ([B, num_levels*(2r+1)^2, H, W]); r <= 8.  Takes
+ *                           the output flags on `radius` (dxr_alt_corr_lookup),
+ *                           every combination at every radius.
  * With finite operands inside the f16 pair's range the outputs are
  * dxr_alt_corr_lookup's bit for bit.  Replaces core/corr.py:74-91 (levels
  * >= first_level) with the reference's alt_cuda_corr semantics.  ABI 9.

@@ -20,9 +20,11 @@ ABI_VERSION = 10
 DXR_OK, DXR_EINVAL, DXR_EUNSUPPORTED, DXR_EHIP = 0, 1, 2, -1
 DXR_F32, DXR_BF16, DXR_F16 = 0, 1, 2   # DXR_F16: an in_dtype of the pyramid builds only
 DXR_PYR_F16 = 4   # float16 pyramid storage: a pyr_dtype only (build, unpack / pack, the lookups)
-# output dtype flags, or-ed onto the pyr_dtype of dxr_corr_lookup / dxr_corr_lookup_conv1x1 only
+# output dtype flags, or-ed onto the pyr_dtype of dxr_corr_lookup / dxr_corr_lookup_conv1x1 and
+# onto the radius of the alternate block's lookups (dxr_alt_corr_lookup, _ws, _levels_ws,
+# dxr_alt_volume_lookup: the low byte is the radius)
 DXR_OUT_F16, DXR_OUT_BF16 = 0x100, 0x200
-# output layout flag of the same two calls: `out` is [B, H, W, C] (channels-last); alone or with
+# output layout flag of the same calls: `out` is [B, H, W, C] (channels-last); alone or with
 # one dtype flag
 DXR_OUT_NHWC = 0x1000
 DXR_NCHW, DXR_NHWC = 0, 1

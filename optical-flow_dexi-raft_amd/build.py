@@ -51,7 +51,11 @@ def _sources(experiments: bool = False) -> list[Path]:
         # and float16-pyramid and channels-last instantiations
         return sorted(EXP_DIR.glob("*.hip")) + [CSRC / "capi.hip", CSRC / "corr_lookup_out16.hip",
                                                 CSRC / "corr_lookup_pyr16.hip",
-                                                CSRC / "corr_lookup_nhwc.hip"]
+                                                CSRC / "corr_lookup_nhwc.hip",
+                                                # the alternate lookups' flagged forms (xp_alt's and
+                                                # xp_lookup's entry points call them)
+                                                CSRC / "corr_lookup_alt_out.hip",
+                                                CSRC / "alt_corr_out.hip"]
     return sorted(CSRC.glob("*.hip"))
 
 
@@ -74,7 +78,8 @@ def is_stale(lib: Path = LIB_PATH) -> bool:
 FILE_FLAGS = {"corr_build.hip": ["-fno-slp-vectorize"], "corr_lookup.hip": ["-fno-slp-vectorize"],
               "corr_lookup_out16.hip": ["-fno-slp-vectorize"],
               "corr_lookup_pyr16.hip": ["-fno-slp-vectorize"],
-              "corr_lookup_nhwc.hip": ["-fno-slp-vectorize"]}
+              "corr_lookup_nhwc.hip": ["-fno-slp-vectorize"],
+              "corr_lookup_alt_out.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src: Path, extra: list[str], out_dir: Path = BUILD_DIR) -> Path:

@@ -867,8 +867,24 @@ class AlternateCorrBlock:
     2^num_levels in either dimension raise (core/corr.py:69-71).
     bfloat16 and float16 fmaps are widened exactly to float32 first (the
     reference's own cast, core/raft.py:139-142).
-    ``__call__`` takes no ``out_dtype`` (CorrBlock's 16-bit lookup outputs): this
-    block's output stores are a separate matter and its result stays float32.
+
+    ``out_dtype`` (None / torch.float32, torch.float16, torch.bfloat16) and
+    ``memory_format`` (None / torch.contiguous_format, torch.channels_last) are
+    keyword-only constructor arguments — the consumer is the same for all of a block's
+    lookups — and anything else raises ``ValueError`` before the native library
+    is reached; ``__call__(coords)`` keeps the reference's signature.  Every
+    lookup then returns ``[B, num_levels*(2r+1)^2, H, W]`` of that dtype with
+    those strides, equal bit for bit to the default block's float32 contiguous
+    result converted with ``.to(out_dtype)`` /
+    ``.contiguous(memory_format=torch.channels_last)``: the kernels store it so
+    themselves (``DXR_OUT_F16`` / ``DXR_OUT_BF16`` / ``DXR_OUT_NHWC`` on the
+    ``radius`` argument of the native calls; the float32 sums rounded to nearest
+    even in the store, float16 overflow to +-inf, NaN bits as torch's conversion
+    gives them), without the float32 tensor,
+    the cast kernel or the layout copy.  The MFMA forms (D % 16 == 0, D <= 256:
+    every RAFT model) and the volume lookup do this natively; for other D the
+    library declines the flags (``DXR_EUNSUPPORTED``) and ``_lookup`` runs the
+    float32 NCHW call and converts with torch — the same tensor by definition.
     """
 
     # Which levels are precomputed (round 6, bench.py --block alt, profiles/r06/experiments/
@@ -884,9 +900,14 @@ class AlternateCorrBlock:
     # pairs/s, two rounds each on one box), so off.
     COARSE_VOLUME_PLANES = False
 
-    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, out_dtype=None,
+                 memory_format=None):
         self.num_levels = num_levels
         self.radius = radius
+        self._out_torch, self._out_flags = _out_flag(out_dtype)
+        self._out_layout = _layout_flag(memory_format)
+        self._out_flags |= self._out_layout
+        self._out_native = True   # until the library declines the flags (a VALU form)
         B, D, H, W = _fmap_geometry(fmap1, fmap2)
         _require_no_grad(fmap1, fmap2, what="AlternateCorrBlock (the reference's alt_cuda_corr "
                                             "output carries no autograd graph, core/corr.py:85-88)")
@@ -921,6 +942,16 @@ class AlternateCorrBlock:
         self._volumes = None
         if D % 16 == 0 and D <= 256 and radius <= 6 and B > 0 and H * W >= self.COARSE_MIN_QUERIES:
             self._make_volumes(B, D, H, W)
+
+    # Introspection reports the reference's constructor (core/corr.py:64), as
+    # CorrBlock's does: ``out_dtype`` and ``memory_format`` are extensions on top
+    # of its four arguments (class docstring; tests/test_api_cpu.py).
+    __init__.__signature__ = inspect.Signature([
+        inspect.Parameter("self", inspect.Parameter.POSITIONAL_OR_KEYWORD),
+        inspect.Parameter("fmap1", inspect.Parameter.POSITIONAL_OR_KEYWORD),
+        inspect.Parameter("fmap2", inspect.Parameter.POSITIONAL_OR_KEYWORD),
+        inspect.Parameter("num_levels", inspect.Parameter.POSITIONAL_OR_KEYWORD, default=4),
+        inspect.Parameter("radius", inspect.Parameter.POSITIONAL_OR_KEYWORD, default=4)])
 
     def _make_volumes(self, B, D, H, W):
         lib = nat.load()
@@ -977,10 +1008,29 @@ class AlternateCorrBlock:
         return self._lookup(c)
 
     def _lookup(self, c):
+        # (a declined request is remembered: later lookups go straight to the fallback)
+        out = self._launch_lookup(c, self._out_flags) if self._out_native else None
+        if out is None:
+            self._out_native = False
+            # a VALU form (D % 16 != 0 or D > 256) declined the flags: the float32
+            # NCHW lookup, converted — the same tensor by definition
+            out = self._launch_lookup(c, 0).to(self._out_torch)
+            if self._out_layout:
+                out = out.contiguous(memory_format=torch.channels_last)
+        return out
+
+    def _launch_lookup(self, c, flags):
+        """One lookup with output ``flags`` or-ed onto the radius; None when the
+        library declines a flagged request (``DXR_EUNSUPPORTED``)."""
         B, D, H, W = self._geom
         rd = 2 * self.radius + 1
-        out = torch.empty((B, self.num_levels * rd * rd, H, W), dtype=torch.float32,
-                          device=self._device)
+        if flags:
+            out = _empty_out((B, self.num_levels * rd * rd, H, W), self._out_torch, self._device,
+                             self._out_layout)
+        else:
+            out = torch.empty((B, self.num_levels * rd * rd, H, W), dtype=torch.float32,
+                              device=self._device)
+        radius = self.radius | flags
         lib = nat.load()
         first = self.coarse_first_level
         if first is None:
@@ -991,8 +1041,10 @@ class AlternateCorrBlock:
             with _Launch(self._device):
                 st = lib.dxr_alt_corr_lookup_ws(self._f1_nhwc.data_ptr(), self._f2_ptrs,
                                                 c.data_ptr(), out.data_ptr(), B, H, W, D,
-                                                self.num_levels, self.radius, _sqrt_dim(D),
+                                                self.num_levels, radius, _sqrt_dim(D),
                                                 nat.ptr(ws), max(nbytes, 0), nat.stream_of(c))
+            if flags and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
+                return None
             nat.check(st, "AlternateCorrBlock lookup (dxr_alt_corr_lookup_ws)")
             return out
         with _Launch(self._device):
@@ -1001,12 +1053,14 @@ class AlternateCorrBlock:
                 ws = torch.empty(max(nbytes, 0), dtype=torch.uint8, device=self._device)
                 st = lib.dxr_alt_corr_lookup_levels_ws(self._f1_nhwc.data_ptr(), self._f2_ptrs,
                                                        c.data_ptr(), out.data_ptr(), B, H, W, D,
-                                                       self.num_levels, first, self.radius,
+                                                       self.num_levels, first, radius,
                                                        _sqrt_dim(D), nat.ptr(ws), max(nbytes, 0),
                                                        nat.stream_of(c))
+                if flags and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
+                    return None
                 nat.check(st, "AlternateCorrBlock lookup (dxr_alt_corr_lookup_levels_ws)")
             st = lib.dxr_alt_volume_lookup(self._volumes.data_ptr(), c.data_ptr(), out.data_ptr(),
-                                           B, H, W, self.num_levels, first, self.radius,
+                                           B, H, W, self.num_levels, first, radius,
                                            _sqrt_dim(D), nat.stream_of(c))
         nat.check(st, "AlternateCorrBlock lookup (dxr_alt_volume_lookup)")
         return out

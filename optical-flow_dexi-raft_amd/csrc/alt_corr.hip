@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "dxr_common.h"
+#include "out_store.h"
 
 namespace {
 
@@ -277,14 +278,22 @@ __device__ __forceinline__ void alt_split8h(const float (&x)[8], uint4& h, uint4
 // a non-finite sum is recomputed on the bf16 split in either form, and chunks
 // group different cells in the two forms).  Tile order only (BIN = false);
 // coordinates are not read.
+// OUTX (alt_corr_out.hip only): the flagged output forms of the lookup — `okind`
+// bit 0: float16 elements, bit 1: bfloat16 (DXR_OUT_F16 / DXR_OUT_BF16: the
+// float32 result converted in the store, out_store.h), bit 2: channels-last
+// (DXR_OUT_NHWC: element (z, ch, q) at (z N + q) cout + ch).  Everything up to
+// the bilinear combination is the float32 NCHW form's code; without OUTX `okind`
+// is not read and the kernel is the one it was.
 template <int R, int NRB, int CMAX, bool H2 = false, int MINW = 2, bool BIN = false, int PF = 1,
-          int DMA = 0, int XP = 0, bool FULL = false>
+          int DMA = 0, int XP = 0, bool FULL = false, bool OUTX = false>
 __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* __restrict__ f1,
                                                                const float* __restrict__ coords,
                                                                float* __restrict__ out,
                                                                AltGeom g, int W1, int tiles_x,
                                                                const int4* __restrict__ ord,
-                                                               long long ord_stride, int XL) {
+                                                               long long ord_stride, int XL,
+                                                               int okind) {
+  static_assert(!OUTX || (!FULL && XP == 0), "flagged outputs: the product lookup only");
   constexpr int RD = 2 * R + 1, RD1 = RD + 1, NCELL = RD1 * RD1;
   constexpr int CHUNK = 4 * 32 * NRB;                       // box cells per chunk
   constexpr int KB = CMAX / 8;                              // 8-channel blocks
@@ -752,6 +761,115 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
   if constexpr (FULL) return;
   __syncthreads();
 
+  if constexpr (OUTX) {
+    // ---- the flagged forms: the combination below, stored as `okind` says
+    const int qq = tid & (TQ - 1), cls = tid / TQ;
+    const int q = query_of(qq);
+    // (channels-last: padding slots stay for the barrier below, on query 0's coordinates)
+    if ((okind & 4) == 0) {
+      if (q < 0) return;
+    }
+    const int qs = max(q, 0);
+    float cx, cy;
+    if constexpr (BIN) {
+      cx = qxy[qq].x;
+      cy = qxy[qq].y;
+    } else {
+      cx = cz[(long long)qs * g.coord_qstride];
+      cy = cz[(long long)qs * g.coord_qstride + g.coord_cstride];
+    }
+    // the float32 NCHW form's arithmetic (below) as the compiler issues it there,
+    // instruction by instruction (out_store.h, "Pinned float32 arithmetic"): the
+    // fractions c * inv - floor(c * inv) fused, 1 - d, then the combination
+    const float dx = dxr::pin_fma_neg(lv.inv, cx, floorf(lv.inv * cx));
+    const float dy = dxr::pin_fma_neg(lv.inv, cy, floorf(lv.inv * cy));
+    const float gx = dxr::pin_sub(1.f, dx), gy = dxr::pin_sub(1.f, dy);
+    const float* s = S + qq * SP;
+    // `put` stores output (oy, ox) of query q
+    auto combine = [&](auto&& put) {
+      for (int ox = cls; ox < RD; ox += 256 / TQ) {
+#pragma unroll
+        for (int oy = 0; oy < RD; ++oy) {
+          const float s00 = s[oy * RD1 + ox], s01 = s[oy * RD1 + ox + 1];
+          const float s10 = s[(oy + 1) * RD1 + ox], s11 = s[(oy + 1) * RD1 + ox + 1];
+          const float v = R == 0
+              ? dxr::alt_combine_pinned_r0(s00, s01, s10, s11, dx, dy, gx, gy)
+              : dxr::alt_combine_pinned<false>(s00, s01, s10, s11, dx, dy, gx, gy);
+          // v / divisor; a power-of-two divisor (sqrt(256) = 16) scales exactly by its reciprocal
+          const float res = g.div_recip != 0.f ? v * g.div_recip : v / g.divisor;
+          put(oy, ox, res);
+        }
+      }
+    };
+    const bool f16 = (okind & 1) != 0, is16 = (okind & 3) != 0;
+    auto bits16 = [&](float r) -> uint32_t {
+      return f16 ? dxr::out16_bits<_Float16>(r) : dxr::out16_bits<__bf16>(dxr::bf16_nan_as_torch(r));
+    };
+    uint16_t* o16 = reinterpret_cast<uint16_t*>(out);
+    const int bpar = dxr::out16_base_parity(o16);
+    if ((okind & 4) == 0) {
+      // NCHW, 16-bit elements: element (ch, q) of this set at e = (z cout + ch) N + q.
+      // Lanes 2i, 2i + 1 swap their 16 bits by DPP, and where they hold queries
+      // q, q + 1 (a tile row's neighbours; seldom in bin order) and the even
+      // lane's element sits on a 4-byte boundary, the even lane stores one word
+      // for both; every other lane stores its own 2 bytes.  No store touches a
+      // byte outside its element(s).  A lane whose partner has left (padding)
+      // reads its own q back and stores alone.
+      const int qn = __builtin_amdgcn_update_dpp(q, q, 0xB1, 0xF, 0xF, false);
+      const bool even = (lane & 1) == 0;
+      const bool pair = even ? qn == q + 1 : qn == q - 1;
+      const long long e0 = ((long long)z * g.cout + lv.ch_off) * g.N + q;
+      combine([&](int oy, int ox, float res) {
+        const long long e = e0 + (long long)(oy + RD * ox) * g.N;
+        const uint32_t h = bits16(res);
+        const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp((int)h, (int)h, 0xB1, 0xF, 0xF, false);
+        const long long ee = even ? e : e - 1;     // the pair's even lane's element
+        const bool word = pair && (((int)(ee & 1) + bpar) & 1) == 0;
+        if (!(word && !even)) dxr::store_out16_one<uint16_t, 0>(o16 + e, h, h | (nb << 16), word);
+      });
+      return;
+    }
+    // Channels-last: query q's K = (2r+1)^2 values of this level are one run at
+    // (z N + q) cout + ch_off.  They are staged in LDS (the query operand planes,
+    // dead after the k loops; odd pitch KP) and written with lanes along the run:
+    // a wave store covers 256 consecutive bytes of a run (128 at 16 bits) and
+    // goes on in the next query's.  16-bit: a lane takes one 4-byte aligned word
+    // of the run (the run starts at an odd element when ch_off, cout or the base
+    // make it so) and the run's first / last lone element 2 bytes.
+    constexpr int K = RD * RD, KP = K | 1;
+    static_assert(TQ * KP * 4 <= (int)sizeof(qplanes), "the staged runs fit the operand planes");
+    float* stage = reinterpret_cast<float*>(qplanes);
+    combine([&](int oy, int ox, float res) {
+      if (q >= 0) stage[qq * KP + oy + RD * ox] = res;
+    });
+    __syncthreads();
+    const long long pix0 = (long long)z * g.N;
+    if (!is16) {
+      for (int i = tid; i < TQ * K; i += 256) {
+        const int rq = i / K, kk = i - rq * K;
+        const int qr = query_of(rq);
+        if (qr >= 0) out[(pix0 + qr) * g.cout + lv.ch_off + kk] = stage[rq * KP + kk];
+      }
+    } else {
+      constexpr int NS = K / 2 + 1;   // word slots per run, either parity
+      for (int i = tid; i < TQ * NS; i += 256) {
+        const int rq = i / NS, sl = i - rq * NS;
+        const int qr = query_of(rq);
+        if (qr < 0) continue;
+        const long long e = (pix0 + qr) * g.cout + lv.ch_off;   // the run's first element
+        const int par = ((int)(e & 1) + bpar) & 1;
+        const int k0 = 2 * sl - par, k1 = k0 + 1;
+        const bool in0 = k0 >= 0 && k0 < K, in1 = k1 < K;       // k1 >= 0 always
+        if (!in0 && !in1) continue;
+        const float* rr = stage + rq * KP;
+        const uint32_t h0 = bits16(rr[in0 ? k0 : k1]), h1 = bits16(rr[in1 ? k1 : k0]);
+        if (in0 && in1) *reinterpret_cast<uint32_t*>(o16 + e + k0) = h0 | (h1 << 16);
+        else if (in0) o16[e + k0] = (uint16_t)h0;
+        else o16[e + k1] = (uint16_t)h1;
+      }
+    }
+    return;
+  }
   // ---- bilinear combination, as the per-query form (reference order)
   const int qq = tid & (TQ - 1), cls = tid / TQ;
   const int q = query_of(qq);
@@ -1046,10 +1164,11 @@ long long alt_order_bytes(long long H, long long W) {
 // (hipcc: "desired occupancy 3, final 2"), so those radii ask for 2.
 constexpr int alt_minw(int r) { return r >= 6 ? 2 : 3; }
 
-template <int R, int NRB, int DMA = 0, int PF = 4, int XP = 0>
+// OUTX / okind: the flagged output forms (alt_corr_mfma_kernel), tile order and ordered.
+template <int R, int NRB, int DMA = 0, int PF = 4, int XP = 0, bool OUTX = false>
 int launch_alt_mfma_r(const float* f1, const float* coords, float* out, const AltGeom& g,
                       int levels, int Z, int W1, hipStream_t stream, void* ws = nullptr,
-                      int xl = -1) {
+                      int xl = -1, int okind = 0) {
   const int H1 = g.N / W1;
   const int tiles_x = (W1 + TQX - 1) / TQX, tiles_y = (H1 + TQY - 1) / TQY;
   const int ntiles = tiles_x * tiles_y;
@@ -1091,15 +1210,15 @@ int launch_alt_mfma_r(const float* f1, const float* coords, float* out, const Al
     if constexpr (DMA != 0)
       hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, 2, true, 1, DMA>), grid,
                          dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x,
-                         reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL);
+                         reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL, 0);
     else
-      hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw(R), true, PF, 0, XP>), grid, dim3(256),
-                         0, stream, f1, coords, out, g, W1, tiles_x,
-                         reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL);
+      hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw(R), true, PF, 0, XP, false, OUTX>),
+                         grid, dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x,
+                         reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL, okind);
     return dxr::launch_status();
   }
-  hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw(R)>), grid, dim3(256), 0, stream, f1,
-                     coords, out, g, W1, tiles_x, nullptr, 0, 0);
+  hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw(R), false, 1, 0, 0, false, OUTX>), grid,
+                     dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x, nullptr, 0, 0, okind);
   return dxr::launch_status();
 }
 
@@ -1114,24 +1233,34 @@ int launch_alt_r(const float* f1, const float* coords, float* out, const AltGeom
   return dxr::launch_status();
 }
 
+// OUTX / okind: a flagged request (alt_corr_out.hip).  The MFMA forms implement
+// every flag combination; the VALU forms decline (DXR_EUNSUPPORTED, nothing
+// launched): a caller runs the unflagged call and converts.
+template <bool OUTX = false>
 int launch_alt(const float* f1, const float* coords, float* out, const AltGeom& g, int levels,
                int Z, int radius, bool vec, hipStream_t stream, int W1 = 0,
-               void* ord = nullptr) {
+               void* ord = nullptr, int okind = 0) {
   // MFMA form: C a multiple of 16 (k16 steps) up to 256, 16-byte aligned rows;
   // the per-query VALU form otherwise.  With a workspace (`ord`) the queries are
   // ordered first (alt_bin_*_kernel).
   if (vec && W1 > 0 && g.C % 16 == 0 && g.C <= 256) {
+#define DXR_ALT_MFMA(RR)                                                                       \
+  case RR:                                                                                     \
+    return launch_alt_mfma_r<RR, 1, 0, 4, 0, OUTX>(f1, coords, out, g, levels, Z, W1, stream, \
+                                                   ord, -1, okind);
     switch (radius) {
-      case 0: return launch_alt_mfma_r<0, 1>(f1, coords, out, g, levels, Z, W1, stream, ord);
-      case 1: return launch_alt_mfma_r<1, 1>(f1, coords, out, g, levels, Z, W1, stream, ord);
-      case 2: return launch_alt_mfma_r<2, 1>(f1, coords, out, g, levels, Z, W1, stream, ord);
-      case 3: return launch_alt_mfma_r<3, 1>(f1, coords, out, g, levels, Z, W1, stream, ord);
-      case 4: return launch_alt_mfma_r<4, 1>(f1, coords, out, g, levels, Z, W1, stream, ord);
-      case 5: return launch_alt_mfma_r<5, 1>(f1, coords, out, g, levels, Z, W1, stream, ord);
-      case 6: return launch_alt_mfma_r<6, 1>(f1, coords, out, g, levels, Z, W1, stream, ord);
+      DXR_ALT_MFMA(0)
+      DXR_ALT_MFMA(1)
+      DXR_ALT_MFMA(2)
+      DXR_ALT_MFMA(3)
+      DXR_ALT_MFMA(4)
+      DXR_ALT_MFMA(5)
+      DXR_ALT_MFMA(6)
       default: return DXR_EUNSUPPORTED;
     }
+#undef DXR_ALT_MFMA
   }
+  if constexpr (OUTX) return DXR_EUNSUPPORTED;
   switch (radius) {
     case 0: return launch_alt_r<0>(f1, coords, out, g, levels, Z, vec, stream);
     case 1: return launch_alt_r<1>(f1, coords, out, g, levels, Z, vec, stream);
@@ -1153,6 +1282,7 @@ float pow2_recip(float d) {
   return (m == 0.5f && e > -125 && e < 126) ? 1.f / d : 0.f;
 }
 
+#ifndef DXR_ALT_OUT_TU   // alt_corr_out.hip takes the lookup's flagged forms only
 // ---------------------------------------------------------------------------
 // alt_cuda_corr.backward, reference-FFI form (correlation_kernel.cu:122-256,
 // launched by :288-320).  For query q of pair b and coordinate set n, cell
@@ -1364,8 +1494,11 @@ __global__ __launch_bounds__(256) void avg_pool2x2_nhwc_kernel(const float* __re
   }
 }
 
+#endif  // DXR_ALT_OUT_TU
+
 }  // namespace
 
+#ifndef DXR_ALT_OUT_TU
 extern "C" int dxr_alt_corr_forward(const float* fmap1, const float* fmap2, const float* coords,
                                     float* corr, int64_t B, int64_t H1, int64_t W1, int64_t H2,
                                     int64_t W2, int64_t C, int64_t Nc, int radius,
@@ -1470,13 +1603,17 @@ extern "C" int dxr_avg_pool2x2_nhwc(const float* in, float* out, int64_t B, int6
   return dxr::launch_status();
 }
 
+#endif  // DXR_ALT_OUT_TU
+
 namespace {
 // n_levels < 0: every level; else only levels [0, n_levels) of a num_levels-level
 // output (the rest come from dxr_alt_volume_lookup).
+// OUTX / okind: a flagged request (launch_alt); `out` then holds what okind says.
+template <bool OUTX = false>
 int alt_lookup(const float* fmap1, const float* const* fmap2_levels, const float* coords, float* out,
                int64_t B, int64_t H, int64_t W, int64_t C, int num_levels, int radius,
                float divisor, void* workspace, int64_t workspace_bytes, hipStream_t stream,
-               int n_levels = -1) {
+               int n_levels = -1, int okind = 0) {
   dxr::Levels L;
   if (!dxr::make_levels(B, H, W, num_levels, &L)) return DXR_EINVAL;
   if (n_levels > num_levels || n_levels == 0) return DXR_EINVAL;
@@ -1508,9 +1645,26 @@ int alt_lookup(const float* fmap1, const float* const* fmap2_levels, const float
   if (workspace != nullptr && aligned16(workspace) &&
       workspace_bytes >= (long long)B * nl * alt_order_bytes(H, W))
     ord = workspace;
-  return launch_alt(fmap1, coords, out, g, nl, (int)B, radius, vec, stream, (int)W, ord);
+  return launch_alt<OUTX>(fmap1, coords, out, g, nl, (int)B, radius, vec, stream, (int)W, ord, okind);
 }
 
+#ifdef DXR_ALT_OUT_TU
+}  // namespace
+
+// alt_corr_out.hip: this file's lookup with the flagged output forms, and nothing
+// else of it.
+int dxr::alt_lookup_out(const float* fmap1, const float* const* fmap2_levels, const float* coords,
+                        void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W,
+                        int64_t C, int num_levels, int radius, float divisor, void* workspace,
+                        int64_t workspace_bytes, hipStream_t stream, int n_levels) {
+  const int okind = (out_flag == DXR_OUT_F16 ? 1 : 0) | (out_flag == DXR_OUT_BF16 ? 2 : 0) |
+                    (nhwc ? 4 : 0);
+  if (okind == 0) return DXR_EINVAL;   // unflagged requests stay in alt_corr.hip
+  return alt_lookup<true>(fmap1, fmap2_levels, coords, static_cast<float*>(out), B, H, W, C,
+                          num_levels, radius, divisor, workspace, workspace_bytes, stream, n_levels,
+                          okind);
+}
+#else
 // ---------------------------------------------------------------------------
 // A coarse level's whole volume as one tiled GEMM (round 6): every (query, cell)
 // sum of the level, raw, into that level's pages of the volume buffer — the FULL
@@ -1947,7 +2101,7 @@ int alt_coarse_volumes(const float* fmap1, const float* const* fmap2_levels, int
     hipLaunchKernelGGL((alt_corr_mfma_kernel<0, 1, 256, true, 3, false, 4, 0, 0, true>),
                        dim3((unsigned)ntiles, 1u, (unsigned)B), dim3(256), 0, stream, fmap1,
                        (const float*)nullptr, volumes, g, (int)W, tiles_x, (const int4*)nullptr,
-                       0LL, 0);
+                       0LL, 0, 0);
     const int st = dxr::launch_status();
     if (st != DXR_OK) return st;
   }
@@ -1980,12 +2134,36 @@ extern "C" int dxr_alt_coarse_volumes_ws(const float* fmap1, const float* const*
                             stream, false, workspace, workspace_bytes);
 }
 
+namespace {
+// The three lookup entry points after their own checks: the output flags or-ed
+// onto `radius` (DXR_OUT_F16 / DXR_OUT_BF16 / DXR_OUT_NHWC, low byte: the radius)
+// are split off first — an invalid combination is DXR_EINVAL before anything
+// else — and a flagged request goes to the flagged forms' translation unit.
+int alt_lookup_entry(const float* fmap1, const float* const* fmap2_levels, const float* coords,
+                     float* out, int64_t B, int64_t H, int64_t W, int64_t C, int num_levels,
+                     int radius, float divisor, void* workspace, int64_t workspace_bytes,
+                     hipStream_t stream, int n_levels) {
+  if (radius >= 0) {
+    int out_flag;
+    bool nhwc;
+    if (!dxr::split_out_flags(&radius, &out_flag, &nhwc)) return DXR_EINVAL;
+    if (out_flag != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return DXR_EINVAL;
+    if (out_flag != 0 || nhwc)
+      return dxr::alt_lookup_out(fmap1, fmap2_levels, coords, out, out_flag, nhwc, B, H, W, C,
+                                 num_levels, radius, divisor, workspace, workspace_bytes, stream,
+                                 n_levels);
+  }
+  return alt_lookup(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
+                    workspace, workspace_bytes, stream, n_levels);
+}
+}  // namespace
+
 extern "C" int dxr_alt_corr_lookup(const float* fmap1, const float* const* fmap2_levels,
                                    const float* coords, float* out, int64_t B, int64_t H,
                                    int64_t W, int64_t C, int num_levels, int radius,
                                    float divisor, hipStream_t stream) {
-  return alt_lookup(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
-                    nullptr, 0, stream);
+  return alt_lookup_entry(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
+                          nullptr, 0, stream, -1);
 }
 
 extern "C" int64_t dxr_alt_workspace_bytes(int64_t B, int64_t H, int64_t W, int num_levels) {
@@ -1999,8 +2177,8 @@ extern "C" int dxr_alt_corr_lookup_ws(const float* fmap1, const float* const* fm
                                       int64_t W, int64_t C, int num_levels, int radius,
                                       float divisor, void* workspace, int64_t workspace_bytes,
                                       hipStream_t stream) {
-  return alt_lookup(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
-                    workspace, workspace_bytes, stream);
+  return alt_lookup_entry(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
+                          workspace, workspace_bytes, stream, -1);
 }
 
 extern "C" int dxr_alt_corr_lookup_levels_ws(const float* fmap1, const float* const* fmap2_levels,
@@ -2008,8 +2186,14 @@ extern "C" int dxr_alt_corr_lookup_levels_ws(const float* fmap1, const float* co
                                              int64_t W, int64_t C, int num_levels, int n_levels,
                                              int radius, float divisor, void* workspace,
                                              int64_t workspace_bytes, hipStream_t stream) {
+  {   // invalid output flags answer first, as in the other lookups
+    int r = radius, f;
+    bool n;
+    if (radius >= 0 && !dxr::split_out_flags(&r, &f, &n)) return DXR_EINVAL;
+  }
   if (n_levels < 1) return DXR_EINVAL;
-  return alt_lookup(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
-                    workspace, workspace_bytes, stream, n_levels);
+  return alt_lookup_entry(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
+                          workspace, workspace_bytes, stream, n_levels);
 }
+#endif  // DXR_ALT_OUT_TU
 

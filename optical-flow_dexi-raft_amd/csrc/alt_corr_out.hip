@@ -1,0 +1,10 @@
+// The on-the-fly lookup's flagged output forms (DXR_OUT_F16 / DXR_OUT_BF16 /
+// DXR_OUT_NHWC on the `radius` of dxr_alt_corr_lookup, dxr_alt_corr_lookup_ws and
+// dxr_alt_corr_lookup_levels_ws): alt_corr.hip's alt_corr_mfma_kernel with
+// OUTX = true, tile order and ordered, radius 0..6; the output dtype and layout
+// are a run-time switch in its last phase.  Instantiated in this translation
+// unit so that the float32 NCHW kernels of alt_corr.hip compile exactly as they
+// did without them.  Defines dxr::alt_lookup_out
+// (dxr_common.h), which the entry points call.
+#define DXR_ALT_OUT_TU
+#include "alt_corr.hip"

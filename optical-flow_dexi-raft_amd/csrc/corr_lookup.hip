@@ -35,8 +35,18 @@
 #include <type_traits>
 
 #include "dxr_common.h"
+#include "out_store.h"
 
 namespace {
+
+// conversion and store helpers shared with csrc/alt_corr.hip (out_store.h)
+using dxr::out16_bits;
+using dxr::out16_base_parity;
+using dxr::store_out16_one;
+using dxr::store_policy;
+using dxr::NHWC_WRITE_THROUGH;
+using dxr::NHWC_NON_TEMPORAL;
+using dxr::NHWC_PLAIN;
 
 constexpr int FAR_ORIGIN = -(1 << 29);  // window origin of far / non-finite queries
 
@@ -514,7 +524,9 @@ __device__ __forceinline__ void qm_phase0_taps(const Phase0Coords<R, NT_, QB_>& 
 // outside +-1e8 or with the window wholly off the level the query is far (its
 // staged cells are zeros, its outputs 0 or NaN as the fractions make them, as
 // alt_corr_mfma_kernel's).
-template <int R, int NT_, int QB_>
+// PIN (the flagged forms): the fractions by a pinned v_sub (out_store.h, "Pinned
+// float32 arithmetic"), the instruction the float32 kernels compile x - xf to.
+template <int R, int NT_, int QB_, bool PIN = false>
 __device__ __forceinline__ void qm_phase0_alt(const Phase0Coords<R, NT_, QB_>& c, const LevelAddr& A,
                                               int l, int tid, float2* xs, float2* ys, int2* org) {
   using C = WideCfg<R, NT_, QB_>;
@@ -538,8 +550,10 @@ __device__ __forceinline__ void qm_phase0_alt(const Phase0Coords<R, NT_, QB_>& c
     if (j == 0) org[qq] = live ? make_int2(x0, y0) : make_int2(FAR_ORIGIN, FAR_ORIGIN);
     if (j < RD) {
       const int col = live ? j + (x0 & 3) : 0, row = live ? j : 0;
-      xs[j * Q::XP + qq] = make_float2(__int_as_float(col * QB), __fsub_rn(x, xf));
-      ys[j * Q::XP + qq] = make_float2(__int_as_float(row * Q::RSC * QB), __fsub_rn(y, yf));
+      xs[j * Q::XP + qq] = make_float2(__int_as_float(col * QB),
+                                       PIN ? dxr::pin_sub(x, xf) : __fsub_rn(x, xf));
+      ys[j * Q::XP + qq] = make_float2(__int_as_float(row * Q::RSC * QB),
+                                       PIN ? dxr::pin_sub(y, yf) : __fsub_rn(y, yf));
     }
   }
 }
@@ -666,41 +680,11 @@ __device__ __forceinline__ void qm_gather(const PT* __restrict__ base, int qb0, 
 // query of an odd tail, lanes store their own 16-bit element: no store touches a
 // byte outside its element(s).
 // ---------------------------------------------------------------------------
-template <typename OT>
-__device__ __forceinline__ uint32_t out16_bits(float r) {
-  static_assert(sizeof(OT) == 2, "16-bit output types");
-  // the float32 value as it stands: without this the compiler folds the last fma
-  // and the conversion into v_fma_mixlo_f16, which rounds the exact sum once to
-  // float16 and so breaks ties differently from float32-then-cast
-  asm volatile("" : "+v"(r));
-  return __builtin_bit_cast(uint16_t, static_cast<OT>(r));
-}
-
-// Parity (in elements) of a 2-byte aligned output base.
-template <typename OT>
-__device__ __forceinline__ int out16_base_parity(const OT* out) {
-  return (int)((reinterpret_cast<uintptr_t>(out) >> 1) & 1);
-}
-
-// MODE 0: plain stores; 1: non-temporal; 2: write-through (agent scope), the
-// float32 kernels' forms.  `word_row`: this row's even elements are 4-byte
+// out16_bits (the conversion), out16_base_parity and store_out16_one (MODE 0:
+// plain stores; 1: non-temporal; 2: write-through, agent scope — the float32
+// kernels' forms): out_store.h.  `word_row`: this row's even elements are 4-byte
 // aligned; `odd`: the lane's query is odd; `has_next`: query q + 1 exists (its
 // lane is active).  Both lanes of a pair must call this together.
-template <typename OT, int MODE>
-__device__ __forceinline__ void store_out16_one(OT* p, uint32_t h, uint32_t w, bool word) {
-  if (word) {
-    uint32_t* pw = reinterpret_cast<uint32_t*>(p);
-    if constexpr (MODE == 1) __builtin_nontemporal_store(w, pw);
-    else if constexpr (MODE == 2) __hip_atomic_store(pw, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *pw = w;
-  } else {
-    uint16_t* ph = reinterpret_cast<uint16_t*>(p);
-    if constexpr (MODE == 1) __builtin_nontemporal_store((uint16_t)h, ph);
-    else if constexpr (MODE == 2) __hip_atomic_store(ph, (uint16_t)h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *ph = (uint16_t)h;
-  }
-}
-
 template <typename OT, int MODE>
 __device__ __forceinline__ void store_out16(OT* p, float r, bool word_row, bool odd, bool has_next) {
   const uint32_t h = out16_bits<OT>(r);
@@ -747,17 +731,10 @@ struct NhwcCfg {
   static_assert(wgs(BASE_B + Q::QB * KCP * 4) >= wgs(BASE_B), "occupancy of the NCHW form");
 };
 
-// Store policy of the channels-last forms, a compile-time argument: the product
+// Store policy of the channels-last forms (out_store.h: NHWC_WRITE_THROUGH /
+// NHWC_NON_TEMPORAL / NHWC_PLAIN, store_policy), a compile-time argument: the product
 // instantiates the one its launchers name (launch_lookup_nhwc_r,
 // launch_lookup_conv1x1_r), the experiments target all of them for the A/B.
-enum { NHWC_WRITE_THROUGH = 0, NHWC_NON_TEMPORAL = 1, NHWC_PLAIN = 2 };
-
-template <int POL, typename T>
-__device__ __forceinline__ void store_policy(T* p, T v) {
-  if constexpr (POL == NHWC_NON_TEMPORAL) __builtin_nontemporal_store(v, p);
-  else if constexpr (POL == NHWC_WRITE_THROUGH) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *p = v;
-}
 
 // a * b and acc + a * b (fused) with the operands in exactly this order (see the
 // channels-last phase 2): round to nearest even, as __fmul_rn / fmaf.
@@ -818,10 +795,13 @@ template <int R, typename PT, int NT_ = 512, int QB_ = 32, int UNR = 1, bool BUF
 __global__ __launch_bounds__(NT_) void corr_lookup_qm_kernel(
     const PT* __restrict__ pyr, const float* __restrict__ coords, OT* __restrict__ out,
     LookupGeom g) {
-  static_assert(std::is_same_v<OT, float> || (!ALT && XA == 0), "16-bit outputs: the product lookup only");
-  static_assert(!NHWC || (!ALT && XA == 0), "channels-last outputs: the product lookup only");
+  static_assert(std::is_same_v<OT, float> || XA == 0, "16-bit outputs: not with the timing ablations");
+  static_assert(!NHWC || XA == 0, "channels-last outputs: not with the timing ablations");
   using Q = QmCfg<R, NT_, QB_>;
   constexpr int RD = Q::RD, K = Q::K, QB = Q::QB, RSC = Q::RSC;
+  // ALT with 16-bit and / or channels-last outputs: the float32 NCHW ALT kernel's
+  // arithmetic, pinned instruction by instruction (out_store.h)
+  constexpr bool FLAGGED = ALT && (NHWC || !std::is_same_v<OT, float>);
   __shared__ __attribute__((aligned(16))) float cells[Q::NCELL * QB];
   __shared__ float2 xs[RD * Q::XP];   // {LDS column offset (int bits), fx}
   __shared__ float2 ys[RD * Q::XP];   // {LDS row offset (int bits), fy}
@@ -840,7 +820,7 @@ __global__ __launch_bounds__(NT_) void corr_lookup_qm_kernel(
   {
     Phase0Coords<R, NT_, QB_> c;
     wide_phase0_load<R, NT_, QB_>(coords, g, b, q0, tid, c);
-    if constexpr (ALT) qm_phase0_alt<R, NT_, QB_>(c, A, l, tid, xs, ys, org);
+    if constexpr (ALT) qm_phase0_alt<R, NT_, QB_, FLAGGED>(c, A, l, tid, xs, ys, org);
     else qm_phase0_taps<R, NT_, QB_>(c, A, l, tid, xs, ys, org);
   }
   __syncthreads();
@@ -892,12 +872,20 @@ __global__ __launch_bounds__(NT_) void corr_lookup_qm_kernel(
             // workgroup shapes, every cell and output type, with non-finite
             // coordinates and a NaN level; a compiler that reorders an NCHW
             // instantiation fails those tests.
-            const float nw = nhwc_mul(gx, gy), ne = nhwc_mul(xd.y, gy);
-            const float sw = nhwc_mul(gx, yd.y), se = nhwc_mul(xd.y, yd.y);
-            float r = nhwc_mul(v00, nw);
-            r = nhwc_fmac(r, ne, v01);
-            r = nhwc_fmac(r, sw, v10);
-            r = nhwc_fmac(r, se, v11);
+            float r;
+            if constexpr (ALT) {
+              // the float32 NCHW ALT form's instructions (below, as compiled)
+              r = dxr::alt_combine_pinned<true>(v00, v01, v10, v11, xd.y, yd.y, gx, gy);
+              r = g.div_recip != 0.f ? r * g.div_recip : r / g.divisor;
+              if constexpr (std::is_same_v<OT, __bf16>) r = dxr::bf16_nan_as_torch(r);
+            } else {
+              const float nw = nhwc_mul(gx, gy), ne = nhwc_mul(xd.y, gy);
+              const float sw = nhwc_mul(gx, yd.y), se = nhwc_mul(xd.y, yd.y);
+              r = nhwc_mul(v00, nw);
+              r = nhwc_fmac(r, ne, v01);
+              r = nhwc_fmac(r, sw, v10);
+              r = nhwc_fmac(r, se, v11);
+            }
             res[qq * T::KCP + (k - k0)] = r;
           }
         }
@@ -933,7 +921,11 @@ __global__ __launch_bounds__(NT_) void corr_lookup_qm_kernel(
     const float v00 = p[0], v01 = p[QB], v10 = p[RSC * QB], v11 = p[RSC * QB + QB];
     const float gx = __fsub_rn(1.f, xd.y), gy = __fsub_rn(1.f, yd.y);
     float r;
-    if constexpr (ALT) {
+    if constexpr (FLAGGED) {
+      r = dxr::alt_combine_pinned<true>(v00, v01, v10, v11, xd.y, yd.y, gx, gy);
+      r = g.div_recip != 0.f ? r * g.div_recip : r / g.divisor;
+      if constexpr (std::is_same_v<OT, __bf16>) r = dxr::bf16_nan_as_torch(r);
+    } else if constexpr (ALT) {
       // correlation_kernel.cu:92-114's order, as alt_corr_mfma_kernel
       r = __fmul_rn(__fmul_rn(v00, gy), gx);
       r = __fadd_rn(r, __fmul_rn(__fmul_rn(v01, gy), xd.y));
@@ -1841,6 +1833,91 @@ int corr_lookup_conv1x1_impl(const void* pyramid, int pyr_dtype, int64_t B, int6
   return DXR_EINVAL;
 }
 
+// The alternate block's coarse levels from their volumes (dxr_alt_coarse_volumes),
+// levels [first, num_levels): launch_lookup_r's shapes and output policy.  OT /
+// NHWC: the 16-bit and channels-last stores of the product lookup (above), on this
+// call's channel slice of a num_levels-wide output; instantiated in
+// corr_lookup_alt_out.hip only (float, NCHW: here).
+template <int R, typename OT = float, bool NHWC = false>
+int launch_alt_volume_r(const float* vol, const float* coords, OT* out, const LookupGeom& g0,
+                        int first, int B, hipStream_t stream) {
+  using W = WideCfg<R>;
+  LookupGeom g = g0;
+  const int nl = g.levels - first;
+  const long long wg32 = (long long)((g.N + W::QB - 1) / W::QB) * nl * B;
+  if constexpr (NHWC) {   // launch_lookup_nhwc_r's two shapes, chosen by the rule below
+    if constexpr (R <= 4) {
+      if (wg32 <= 1024) {
+        const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)nl, (unsigned)B);
+        hipLaunchKernelGGL((corr_lookup_qm_kernel<R, float, 256, 16, 1, false, 0, true, OT, true>), grid,
+                           dim3(256), 0, stream, vol, coords, out, g);
+        return dxr::launch_status();
+      }
+    }
+    const dim3 grid((unsigned)((g.N + W::QB - 1) / W::QB), (unsigned)nl, (unsigned)B);
+    hipLaunchKernelGGL((corr_lookup_qm_kernel<R, float, 512, W::QB, 1, true, 0, true, OT, true>), grid,
+                       dim3(512), 0, stream, vol, coords, out, g);
+    return dxr::launch_status();
+  } else {
+  if (R <= 4 && wg32 <= 1024) {
+    g.out_nt = g.N % 32 == 0 ? 1 : 0;
+    const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)nl, (unsigned)B);
+    hipLaunchKernelGGL((corr_lookup_qm_kernel<R, float, 256, 16, 1, false, 0, true, OT>), grid, dim3(256), 0,
+                       stream, vol, coords, out, g);
+    return dxr::launch_status();
+  }
+  g.out_nt = 1;
+  const dim3 grid((unsigned)((g.N + W::QB - 1) / W::QB), (unsigned)nl, (unsigned)B);
+  hipLaunchKernelGGL((corr_lookup_qm_kernel<R, float, 512, W::QB, 1, true, 0, true, OT>), grid, dim3(512), 0,
+                     stream, vol, coords, out, g);
+  return dxr::launch_status();
+  }
+}
+
+// dxr_alt_volume_lookup after its flags: the checks (before any launch), the
+// geometry and the launch.
+template <typename OT, bool NHWC = false>
+int alt_volume_lookup_impl(const float* volumes, const float* coords, OT* out, int64_t B, int64_t H,
+                           int64_t W, int num_levels, int first_level, int radius, float divisor,
+                           hipStream_t stream) {
+  dxr::Levels L;
+  if (!dxr::make_levels(B, H, W, num_levels, &L) || first_level < 0 || first_level >= num_levels)
+    return DXR_EINVAL;
+  if (radius < 0 || !(divisor == divisor) || divisor == 0.f) return DXR_EINVAL;
+  if (radius > 8) return DXR_EUNSUPPORTED;
+  if (B > 65535) return DXR_EINVAL;
+  if (B == 0) return DXR_OK;
+  if (!volumes || !coords || !out) return DXR_EINVAL;
+  const int rd = 2 * radius + 1;
+  LookupGeom g;
+  g.N = (int)(H * W);
+  g.levels = num_levels;
+  g.cout = num_levels * rd * rd;
+  g.l0 = first_level;
+  g.divisor = divisor;
+  {
+    int e;
+    const float m = std::frexp(divisor, &e);
+    g.div_recip = (m == 0.5f && e > -125 && e < 126) ? 1.f / divisor : 0.f;   // exact: a power of two
+  }
+  for (int l = 0; l < L.n; ++l) {
+    g.lv[l] = level_addr(L.lay[l]);
+    g.lv[l].off -= L.off[first_level];
+  }
+  switch (radius) {
+    case 0: return launch_alt_volume_r<0, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 1: return launch_alt_volume_r<1, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 2: return launch_alt_volume_r<2, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 3: return launch_alt_volume_r<3, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 4: return launch_alt_volume_r<4, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 5: return launch_alt_volume_r<5, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 6: return launch_alt_volume_r<6, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 7: return launch_alt_volume_r<7, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 8: return launch_alt_volume_r<8, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
+    default: return DXR_EUNSUPPORTED;
+  }
+}
+
 }  // namespace
 
 #if defined(DXR_LOOKUP_PYR16_TU)
@@ -1906,6 +1983,25 @@ int dxr::lookup_conv1x1_nhwc(const void* pyramid, int pyr_dtype, int out_flag, i
                                                coords, weight_packed, bias, cout, relu,
                                                static_cast<float*>(out), stream);
 }
+#elif defined(DXR_LOOKUP_ALT_OUT_TU)
+// corr_lookup_alt_out.hip: the alternate block's volume lookup with 16-bit and / or
+// channels-last outputs, and nothing else of this file.
+int dxr::alt_volume_lookup_out(const float* volumes, const float* coords, void* out, int out_flag,
+                               bool nhwc, int64_t B, int64_t H, int64_t W, int num_levels,
+                               int first_level, int radius, float divisor, hipStream_t stream) {
+#define DXR_ALT_VOL(OT, NHWC)                                                                    \
+  alt_volume_lookup_impl<OT, NHWC>(volumes, coords, static_cast<OT*>(out), B, H, W, num_levels, \
+                                   first_level, radius, divisor, stream)
+  if (nhwc) {
+    if (out_flag == DXR_OUT_F16) return DXR_ALT_VOL(_Float16, true);
+    if (out_flag == DXR_OUT_BF16) return DXR_ALT_VOL(__bf16, true);
+    return DXR_ALT_VOL(float, true);
+  }
+  if (out_flag == DXR_OUT_F16) return DXR_ALT_VOL(_Float16, false);
+  if (out_flag == DXR_OUT_BF16) return DXR_ALT_VOL(__bf16, false);
+  return DXR_EINVAL;   // unflagged requests stay in corr_lookup.hip
+#undef DXR_ALT_VOL
+}
 #elif defined(DXR_LOOKUP_OUT16_TU)
 // corr_lookup_out16.hip: this file's templates with the 16-bit output types, and
 // nothing else of it.
@@ -1933,71 +2029,22 @@ int dxr::lookup_conv1x1_out16(const void* pyramid, int pyr_dtype, int out_flag, 
 }
 #else   // the entry points (float32 outputs)
 
-namespace {
-// The alternate block's coarse levels from their volumes (dxr_alt_coarse_volumes),
-// levels [first, num_levels): launch_lookup_r's shapes and output policy.
-template <int R>
-int launch_alt_volume_r(const float* vol, const float* coords, float* out, const LookupGeom& g0,
-                        int first, int B, hipStream_t stream) {
-  using W = WideCfg<R>;
-  LookupGeom g = g0;
-  const int nl = g.levels - first;
-  const long long wg32 = (long long)((g.N + W::QB - 1) / W::QB) * nl * B;
-  if (R <= 4 && wg32 <= 1024) {
-    g.out_nt = g.N % 32 == 0 ? 1 : 0;
-    const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)nl, (unsigned)B);
-    hipLaunchKernelGGL((corr_lookup_qm_kernel<R, float, 256, 16, 1, false, 0, true>), grid, dim3(256), 0,
-                       stream, vol, coords, out, g);
-    return dxr::launch_status();
-  }
-  g.out_nt = 1;
-  const dim3 grid((unsigned)((g.N + W::QB - 1) / W::QB), (unsigned)nl, (unsigned)B);
-  hipLaunchKernelGGL((corr_lookup_qm_kernel<R, float, 512, W::QB, 1, true, 0, true>), grid, dim3(512), 0,
-                     stream, vol, coords, out, g);
-  return dxr::launch_status();
-}
-}  // namespace
-
 extern "C" int dxr_alt_volume_lookup(const float* volumes, const float* coords, float* out,
                                      int64_t B, int64_t H, int64_t W, int num_levels,
                                      int first_level, int radius, float divisor,
                                      hipStream_t stream) {
-  dxr::Levels L;
-  if (!dxr::make_levels(B, H, W, num_levels, &L) || first_level < 0 || first_level >= num_levels)
-    return DXR_EINVAL;
-  if (radius < 0 || !(divisor == divisor) || divisor == 0.f) return DXR_EINVAL;
-  if (radius > 8) return DXR_EUNSUPPORTED;
-  if (B > 65535) return DXR_EINVAL;
-  if (B == 0) return DXR_OK;
-  if (!volumes || !coords || !out) return DXR_EINVAL;
-  const int rd = 2 * radius + 1;
-  LookupGeom g;
-  g.N = (int)(H * W);
-  g.levels = num_levels;
-  g.cout = num_levels * rd * rd;
-  g.l0 = first_level;
-  g.divisor = divisor;
-  {
-    int e;
-    const float m = std::frexp(divisor, &e);
-    g.div_recip = (m == 0.5f && e > -125 && e < 126) ? 1.f / divisor : 0.f;   // exact: a power of two
+  int out_flag;
+  bool nhwc;
+  // the output flags on `radius` (DXR_OUT_F16 / DXR_OUT_BF16 / DXR_OUT_NHWC) first
+  if (radius >= 0) {
+    if (!dxr::split_out_flags(&radius, &out_flag, &nhwc)) return DXR_EINVAL;
+    if (out_flag != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return DXR_EINVAL;
+    if (out_flag != 0 || nhwc)   // their own translation unit (corr_lookup_alt_out.hip)
+      return dxr::alt_volume_lookup_out(volumes, coords, out, out_flag, nhwc, B, H, W, num_levels,
+                                        first_level, radius, divisor, stream);
   }
-  for (int l = 0; l < L.n; ++l) {
-    g.lv[l] = level_addr(L.lay[l]);
-    g.lv[l].off -= L.off[first_level];
-  }
-  switch (radius) {
-    case 0: return launch_alt_volume_r<0>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 1: return launch_alt_volume_r<1>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 2: return launch_alt_volume_r<2>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 3: return launch_alt_volume_r<3>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 4: return launch_alt_volume_r<4>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 5: return launch_alt_volume_r<5>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 6: return launch_alt_volume_r<6>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 7: return launch_alt_volume_r<7>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 8: return launch_alt_volume_r<8>(volumes, coords, out, g, first_level, (int)B, stream);
-    default: return DXR_EUNSUPPORTED;
-  }
+  return alt_volume_lookup_impl(volumes, coords, out, B, H, W, num_levels, first_level, radius,
+                                divisor, stream);
 }
 
 namespace {

@@ -1,0 +1,9 @@
+// The alternate block's volume lookup with flagged outputs (DXR_OUT_F16 /
+// DXR_OUT_BF16 / DXR_OUT_NHWC on the `radius` of dxr_alt_volume_lookup): the ALT
+// form of corr_lookup.hip's corr_lookup_qm_kernel with the 16-bit and channels-
+// last stores of the product lookup.  Instantiated in this translation unit so
+// that every other kernel of corr_lookup.hip compiles exactly as it did without
+// them.  Defines dxr::alt_volume_lookup_out
+// (dxr_common.h), which the entry point calls.
+#define DXR_LOOKUP_ALT_OUT_TU
+#include "corr_lookup.hip"

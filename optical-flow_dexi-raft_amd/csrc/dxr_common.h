@@ -54,6 +54,21 @@ int lookup_conv1x1_nhwc(const void* pyramid, int pyr_dtype, int out_flag, int64_
                         const void* weight_packed, const float* bias, int64_t cout, int relu,
                         void* out, hipStream_t stream);
 
+// The alternate block's lookups with output flags on `radius` (split off and
+// validated by the entry points; out_flag 0 / DXR_OUT_F16 / DXR_OUT_BF16, nhwc:
+// DXR_OUT_NHWC; at least one of them set).  alt_lookup_out: dxr_alt_corr_lookup,
+// _ws and _levels_ws (n_levels < 0: every level), defined in alt_corr_out.hip;
+// alt_volume_lookup_out: dxr_alt_volume_lookup, defined in
+// corr_lookup_alt_out.hip.  The only translation units that instantiate those
+// kernels' flagged forms.
+int alt_lookup_out(const float* fmap1, const float* const* fmap2_levels, const float* coords,
+                   void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W, int64_t C,
+                   int num_levels, int radius, float divisor, void* workspace,
+                   int64_t workspace_bytes, hipStream_t stream, int n_levels);
+int alt_volume_lookup_out(const float* volumes, const float* coords, void* out, int out_flag,
+                          bool nhwc, int64_t B, int64_t H, int64_t W, int num_levels,
+                          int first_level, int radius, float divisor, hipStream_t stream);
+
 // ---------------------------------------------------------------------------
 // Pyramid layout ("paged" correlation volume).
 //
