@@ -139,6 +139,15 @@ enum dxr_dtype {
  */
 #define DXR_OUT_NHWC 0x1000
 
+/*
+ * Accumulate flag of dxr_alt_corr_backward, or-ed onto its `radius` argument
+ * (the low byte is the radius): the gradients are added into fmap1_grad and
+ * fmap2_grad by the matrix-core kernel instead of overwriting them.  Semantics,
+ * served shapes and validation: at dxr_alt_corr_backward.  On any other entry
+ * point the bit is an unknown flag.
+ */
+#define DXR_ALT_BWD_ACCUMULATE 0x2000
+
 enum dxr_layout {
   DXR_NCHW = 0,         /* fmaps [B, D, H, W] (core/raft.py:139-142)              */
   DXR_NHWC = 1          /* fmaps [B, H, W, D] (channels-last encoders, §8(f) row 4) */
@@ -530,6 +539,28 @@ int dxr_alt_corr_forward(const float* fmap1, const float* fmap2,
  *                as in the reference)
  * The reference's third output, coords_grad, is identically zero; the caller
  * allocates it.  Radius 0..6.
+ *
+ * DXR_ALT_BWD_ACCUMULATE or-ed onto `radius` (low byte: the radius, 0..6): the
+ * values the unflagged call would write — same mathematics, layouts and channel
+ * order iy + (2r+1)*ix, no 1/sqrt(C) — are ADDED INTO fmap1_grad and fmap2_grad.
+ * No memset is issued: the caller zero-fills (or keeps accumulating into) both.
+ * The call runs one exact-f32 MFMA kernel (v_mfma_f32_32x32x2_f32): a workgroup
+ * takes a 4 x 8 tile of queries, walks the union box of their windows and adds
+ * one float atomic per (box cell, channel) into fmap2_grad instead of one per
+ * (query, cell, channel); fmap1_grad is added by the tile's own workgroup
+ * (atomically when Nc > 1).  Served when C % 16 == 0, C <= 256, B * Nc <= 65535
+ * and the four fmap pointers are 16-byte aligned; other shapes and radius > 6
+ * are DXR_EUNSUPPORTED (callers then use the unflagged call and add).  With the
+ * flag any other bit above the low byte is DXR_EINVAL, null pointers are
+ * DXR_EINVAL and B == 0 is DXR_OK; everything is answered on the host before any
+ * launch, and every `radius` without the bit is answered as it always was.
+ * Contract: finite fmaps and finite corr_grad (the box GEMM multiplies a zero
+ * weight with cells and queries the per-query form never reads, and 0 * inf is
+ * NaN).  Coordinates may be anything: a query with a NaN, infinite or far
+ * (|floor| >= 1e8) coordinate, or whose window lies off the map, has weights
+ * exactly 0 and contributes exactly nothing (the unflagged kernel returns NaN
+ * rows for non-finite coordinates).  fmap2_grad's last bits depend on the
+ * order of the atomics, as above.
  */
 int dxr_alt_corr_backward(const float* fmap1, const float* fmap2,
                           const float* coords, const float* corr_grad,

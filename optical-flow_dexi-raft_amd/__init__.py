@@ -5,6 +5,7 @@ which maps it onto this ``optical-flow_dexi-raft_amd/`` directory).
 
 Public surface, mirroring the reference's interface for this path:
   * ``CorrBlock``, ``AlternateCorrBlock``  — core/corr.py:12-91
+  * ``TrainableAlternateCorrBlock``        — the on-the-fly block with fmap gradients
   * ``alt_cuda_corr.forward / backward``  — alt_cuda_corr/correlation.cpp:51-54
   * ``coords_grid``                        — core/utils/utils.py:74-77
   * ``driver.InputPadder / write_flo / infer_pairs`` — core/utils/utils.py:7-24,
@@ -12,9 +13,9 @@ Public surface, mirroring the reference's interface for this path:
 """
 from . import alt_cuda_corr, driver
 from ._native import LIB_PATH, load as load_native
-from .corr import AlternateCorrBlock, CorrBlock
+from .corr import AlternateCorrBlock, CorrBlock, TrainableAlternateCorrBlock
 from .utils import coords_grid
 
-__all__ = ["CorrBlock", "AlternateCorrBlock", "alt_cuda_corr", "coords_grid", "driver", "load_native",
+__all__ = ["CorrBlock", "AlternateCorrBlock", "TrainableAlternateCorrBlock", "alt_cuda_corr", "coords_grid", "driver", "load_native",
            "LIB_PATH"]
 __version__ = "0.1.0"

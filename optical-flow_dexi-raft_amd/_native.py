@@ -27,6 +27,9 @@ DXR_OUT_F16, DXR_OUT_BF16 = 0x100, 0x200
 # output layout flag of the same calls: `out` is [B, H, W, C] (channels-last); alone or with
 # one dtype flag
 DXR_OUT_NHWC = 0x1000
+# accumulate flag of dxr_alt_corr_backward, or-ed onto its radius: the MFMA kernel adds the
+# gradients into fmap1_grad / fmap2_grad (no memset; the caller zero-fills)
+DXR_ALT_BWD_ACCUMULATE = 0x2000
 DXR_NCHW, DXR_NHWC = 0, 1
 DXR_BUILD_AUTO, DXR_BUILD_EXACT_F32 = 0, 1
 

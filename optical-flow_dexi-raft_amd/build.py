@@ -55,7 +55,10 @@ def _sources(experiments: bool = False) -> list[Path]:
                                                 # the alternate lookups' flagged forms (xp_alt's and
                                                 # xp_lookup's entry points call them)
                                                 CSRC / "corr_lookup_alt_out.hip",
-                                                CSRC / "alt_corr_out.hip"]
+                                                CSRC / "alt_corr_out.hip",
+                                                # the accumulating backward xp_alt's copy of
+                                                # dxr_alt_corr_backward dispatches to
+                                                CSRC / "alt_corr_bwd.hip"]
     return sorted(CSRC.glob("*.hip"))
 
 

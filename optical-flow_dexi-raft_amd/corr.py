@@ -23,6 +23,9 @@ Differences from the reference, all loud:
     detaches them, core/raft.py:170; no grid gradient is implemented), as do
     bfloat16 or float16 fmaps that require grad and AlternateCorrBlock inputs
     that require grad (the reference's alt_cuda_corr output carries no autograd graph).
+
+``TrainableAlternateCorrBlock`` is the on-the-fly block with fmap gradients
+(O(H*W*D) memory in the backward too): same constructor and ``__call__``.
 """
 from __future__ import annotations
 
@@ -35,7 +38,7 @@ import torch
 
 from . import _native as nat
 
-__all__ = ["CorrBlock", "AlternateCorrBlock"]
+__all__ = ["CorrBlock", "AlternateCorrBlock", "TrainableAlternateCorrBlock"]
 
 
 @lru_cache(maxsize=None)
@@ -1064,3 +1067,139 @@ class AlternateCorrBlock:
                                            _sqrt_dim(D), nat.stream_of(c))
         nat.check(st, "AlternateCorrBlock lookup (dxr_alt_volume_lookup)")
         return out
+
+
+class _AltLookupGrad(torch.autograd.Function):
+    """Graph node of one TrainableAlternateCorrBlock lookup: differentiable in the
+    fmaps only.  Saves ``coords``; everything else the backward reads is the
+    block's own O(B*H*W*D) state (NHWC fmap1, the pooled fmap2 levels)."""
+
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, coords, block):
+        ctx.block = block
+        ctx.save_for_backward(coords)
+        return block._lookup(coords)
+
+    @staticmethod
+    def backward(ctx, gout):
+        (coords,) = ctx.saved_tensors
+        df1, df2 = ctx.block._lookup_backward(coords, gout, ctx.needs_input_grad[:2])
+        return df1, df2, None, None
+
+
+class TrainableAlternateCorrBlock(AlternateCorrBlock):
+    """``AlternateCorrBlock`` that can be trained through: O(H*W*D) memory in the
+    forward *and* in the backward (``CorrBlock``, the other trainable block, keeps
+    an O((H*W)^2) pyramid and a gradient pyramid of the same size).
+
+    Without a fmap that requires grad, or with grad mode off, every output is
+    ``AlternateCorrBlock``'s bit for bit and carries no graph.  With float32 fmaps
+    that require grad the forward is still the parent's (coarse volumes,
+    ``out_dtype`` / ``memory_format`` outputs included) and each lookup is one
+    autograd node that saves ``coords`` only.  Its backward makes one
+    ``dxr_alt_corr_backward`` call per level with ``DXR_ALT_BWD_ACCUMULATE`` (the
+    exact-f32 MFMA kernel of csrc/alt_corr_bwd.hip) on the NHWC fmap1, the level's
+    pooled fmap2, ``coords / 2^l`` and the level's channel slice of ``grad_out``
+    (one relayout pass per lookup) into zero-filled fmap-sized buffers, folds the
+    level gradients of fmap2 down the pooling chain (level l gets level l+1's
+    total / 4; the floor-mode remainder row / column gets 0), scales by
+    1 / sqrt(D) and returns ``[B, D, H, W]`` gradients (permuted views); autograd
+    sums the lookups.  Nothing proportional to (H*W)^2 is allocated and nothing
+    but ``coords`` is held per lookup.
+
+    bfloat16 / float16 fmaps that require grad are widened by an autograd-tracked
+    ``.float()``, so their gradients arrive in the input dtype.  D % 16 != 0 or
+    D > 256 (the library declines the flag, ``DXR_EUNSUPPORTED``) runs the
+    unflagged per-query kernel and adds with torch: the same gradients to
+    tolerance, except that that kernel returns NaN for a query with a NaN or
+    infinite coordinate where the MFMA kernel drops it (exactly 0).  Fmaps and
+    ``grad_out`` must be finite.  Coords that require grad raise
+    ``NotImplementedError``, as everywhere; bad ``out_dtype`` / ``memory_format``
+    raise ``ValueError`` before the native library is reached.
+    """
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, out_dtype=None,
+                 memory_format=None):
+        _out_flag(out_dtype)
+        _layout_flag(memory_format)
+        self._train = None
+        self._bwd_native = True   # until the library declines the accumulate flag
+        if isinstance(fmap1, torch.Tensor) and isinstance(fmap2, torch.Tensor) and \
+                _wants_grad(fmap1, fmap2):
+            _fmap_geometry(fmap1, fmap2)
+            if fmap1.dtype in (torch.bfloat16, torch.float16):
+                fmap1, fmap2 = fmap1.float(), fmap2.float()   # tracked: grads in the input dtype
+            self._train = (fmap1, fmap2)
+            fmap1, fmap2 = fmap1.detach(), fmap2.detach()
+        super().__init__(fmap1, fmap2, num_levels, radius, out_dtype=out_dtype,
+                         memory_format=memory_format)
+
+    __init__.__signature__ = AlternateCorrBlock.__init__.__signature__
+
+    def __call__(self, coords):
+        if self._train is None or not torch.is_grad_enabled():
+            return super().__call__(coords)
+        B, D, H, W = self._geom
+        _require_no_grad(coords, what="coords (the reference detaches them, core/raft.py:170)")
+        c = _check_coords(coords, B, H, W, self._device)
+        return _AltLookupGrad.apply(self._train[0], self._train[1], c, self)
+
+    def _level_backward(self, lib, f2, c_l, g_l, f1g, f2g, flags):
+        B, D, H, W = self._geom
+        return lib.dxr_alt_corr_backward(self._f1_nhwc.data_ptr(), f2.data_ptr(), c_l.data_ptr(),
+                                         g_l.data_ptr(), f1g.data_ptr(), f2g.data_ptr(), B, H, W,
+                                         int(f2.shape[1]), int(f2.shape[2]), D, 1,
+                                         self.radius | flags, nat.stream_of(f1g))
+
+    def _lookup_backward(self, coords, gout, needs):
+        """(dfmap1, dfmap2) of one lookup, ``[B, D, H, W]`` float32 views (None
+        where not needed)."""
+        B, D, H, W = self._geom
+        L, rr = self.num_levels, (2 * self.radius + 1) ** 2
+        dev = self._device
+        # one relayout pass: [B, L*rr, H, W] of any dtype / memory format -> the L
+        # contiguous float32 [B, 1, rr, H, W] slices the native call takes
+        g = gout.reshape(B, L, rr, H, W).transpose(0, 1)
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            g = torch.empty((L, B, rr, H, W), dtype=torch.float32, device=dev).copy_(g)
+        # coords / 2^l as [B, 1, H, W, 2] per level (exact: powers of two)
+        scale = torch.tensor([0.5 ** l for l in range(L)], dtype=torch.float32,
+                             device=dev).view(L, 1, 1, 1, 1)
+        cl = (coords.permute(0, 2, 3, 1).unsqueeze(0) * scale).contiguous()
+        f1g = torch.zeros((B, H, W, D), dtype=torch.float32, device=dev)
+        f2g = [torch.zeros_like(t) for t in self._f2_nhwc]
+        lib = nat.load()
+        what = "TrainableAlternateCorrBlock backward (dxr_alt_corr_backward)"
+        with _Launch(dev):
+            for l in range(L):
+                if self._bwd_native:
+                    st = self._level_backward(lib, self._f2_nhwc[l], cl[l], g[l], f1g, f2g[l],
+                                              nat.DXR_ALT_BWD_ACCUMULATE)
+                    if st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
+                        self._bwd_native = False   # remembered, as a declined output flag is
+                    else:
+                        nat.check(st, what)
+                        continue
+                # the library declined the flag (D % 16 != 0, D > 256): the per-query
+                # kernel overwrites, torch adds
+                t1 = torch.empty_like(f1g)
+                nat.check(self._level_backward(lib, self._f2_nhwc[l], cl[l], g[l], t1, f2g[l], 0),
+                          what)
+                f1g += t1
+        inv = 1.0 / _sqrt_dim(D)
+        df1 = df2 = None
+        if needs[0]:
+            df1 = f1g.mul_(inv).permute(0, 3, 1, 2)
+        if needs[1]:
+            # avg_pool2d backward, coarse to fine: every covered cell gets a quarter
+            tot = f2g[L - 1]
+            for l in range(L - 2, -1, -1):
+                q = tot * 0.25
+                Ho, Wo = int(q.shape[1]), int(q.shape[2])
+                fine = f2g[l][:, :2 * Ho, :2 * Wo]
+                for a in range(2):
+                    for b in range(2):
+                        fine[:, a::2, b::2] += q
+                tot = f2g[l]
+            df2 = tot.mul_(inv).permute(0, 3, 1, 2)
+        return df1, df2

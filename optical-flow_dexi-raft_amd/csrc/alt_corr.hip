@@ -1534,6 +1534,10 @@ extern "C" int dxr_alt_corr_backward(const float* fmap1, const float* fmap2, con
                                      hipStream_t stream) {
   if (B < 0 || H1 < 1 || W1 < 1 || H2 < 1 || W2 < 1 || C < 1 || Nc < 0 || radius < 0)
     return DXR_EINVAL;
+  // the accumulating MFMA form (alt_corr_bwd.hip); every other radius as it always was
+  if (radius & DXR_ALT_BWD_ACCUMULATE)
+    return dxr::alt_backward_accumulate(fmap1, fmap2, coords, corr_grad, fmap1_grad, fmap2_grad,
+                                        B, H1, W1, H2, W2, C, Nc, radius, stream);
   if (radius > 6) return DXR_EUNSUPPORTED;
   if (H1 * W1 > (1LL << 30) || H2 * W2 > (1LL << 30) || B > 65535 || C > (1 << 20))
     return DXR_EINVAL;

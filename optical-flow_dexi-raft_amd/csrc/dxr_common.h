@@ -65,6 +65,13 @@ int alt_lookup_out(const float* fmap1, const float* const* fmap2_levels, const f
                    void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W, int64_t C,
                    int num_levels, int radius, float divisor, void* workspace,
                    int64_t workspace_bytes, hipStream_t stream, int n_levels);
+// dxr_alt_corr_backward with DXR_ALT_BWD_ACCUMULATE on `radius` (passed whole; B,
+// the map sizes and C already checked positive, radius >= 0): validation and
+// the MFMA kernel that adds into both gradients.  Defined in alt_corr_bwd.hip.
+int alt_backward_accumulate(const float* fmap1, const float* fmap2, const float* coords,
+                            const float* corr_grad, float* fmap1_grad, float* fmap2_grad,
+                            int64_t B, int64_t H1, int64_t W1, int64_t H2, int64_t W2, int64_t C,
+                            int64_t Nc, int radius, hipStream_t stream);
 int alt_volume_lookup_out(const float* volumes, const float* coords, void* out, int out_flag,
                           bool nhwc, int64_t B, int64_t H, int64_t W, int num_levels,
                           int first_level, int radius, float divisor, hipStream_t stream);
