@@ -148,6 +148,17 @@ enum dxr_dtype {
  */
 #define DXR_ALT_BWD_ACCUMULATE 0x2000
 
+/*
+ * Input dtype flag of dxr_alt_corr_lookup, dxr_alt_corr_lookup_ws and
+ * dxr_alt_corr_lookup_levels_ws, or-ed onto their `radius` argument (the low
+ * byte is the radius), alone or with the output flags: fmap1 and fmap2 level 0
+ * are read as the float16 maps a mixed-precision encoder emits
+ * (core/raft.py:139-142 widens them first), without a float32 copy.  Semantics,
+ * served shapes and validation: "Float16 fmaps on radius" at
+ * dxr_alt_corr_lookup.  On any other entry point the bit is an unknown flag.
+ */
+#define DXR_ALT_IN_F16 0x8000
+
 enum dxr_layout {
   DXR_NCHW = 0,         /* fmaps [B, D, H, W] (core/raft.py:139-142)              */
   DXR_NHWC = 1          /* fmaps [B, H, W, D] (channels-last encoders, §8(f) row 4) */
@@ -606,6 +617,29 @@ int dxr_alt_corr_backward(const float* fmap1, const float* fmap2,
  * every combination natively.  The per-query VALU forms (any other C, or
  * misaligned operands) decline a flagged request with DXR_EUNSUPPORTED and
  * launch nothing; the caller runs the unflagged call and converts.
+ *
+ * Float16 fmaps on radius.  DXR_ALT_IN_F16, or-ed onto the `radius` of
+ * dxr_alt_corr_lookup, dxr_alt_corr_lookup_ws and dxr_alt_corr_lookup_levels_ws,
+ * alone or with any valid combination of the output flags above: fmap1 and
+ * fmap2_levels[0] point at [B, H, W, C] IEEE float16 (through the float*
+ * parameters) — the feature maps a mixed-precision encoder emits, which the
+ * reference widens first (core/raft.py:139-142) — and fmap2_levels[l >= 1] at
+ * float32 as ever: the 2x2 means of the level above, pooled from the widened
+ * level 0, which are not float16 numbers.  The call returns what the unflagged
+ * call returns on the widened float32 copies of the two maps: with finite fmaps
+ * every output is equal as a value (+0 and -0 compare equal) under every output
+ * flag.  Level 0 is one f16 matrix-core product per k step on the raw values and
+ * needs no overflow fallback; the pooled levels issue two products instead of
+ * three.  With inf / NaN in the fmaps the outputs are non-finite exactly where
+ * exact arithmetic's are; the finite outputs of a chunk that the widened call
+ * recomputes on its bf16 split may differ from it in the last bits.
+ * Served when C % 16 == 0, C <= 256, radius <= 6 and fmap1 and every level are
+ * 16-byte aligned; any other C or alignment (the per-query VALU forms have no
+ * float16 variant) and radius > 6 are DXR_EUNSUPPORTED, null pointers DXR_EINVAL,
+ * B == 0 DXR_OK, all answered on the host before any launch; the caller widens
+ * and runs the unflagged call.  dxr_alt_volume_lookup (no fmaps),
+ * dxr_alt_corr_forward / _backward and dxr_alt_coarse_volumes* do not take the
+ * bit: there it is an unknown flag.
  */
 int dxr_alt_corr_lookup(const float* fmap1, const float* const* fmap2_levels,
                         const float* coords, float* out,

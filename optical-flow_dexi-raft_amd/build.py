@@ -56,6 +56,7 @@ def _sources(experiments: bool = False) -> list[Path]:
                                                 # xp_lookup's entry points call them)
                                                 CSRC / "corr_lookup_alt_out.hip",
                                                 CSRC / "alt_corr_out.hip",
+                                                CSRC / "alt_corr_in16.hip",
                                                 # the accumulating backward xp_alt's copy of
                                                 # dxr_alt_corr_backward dispatches to
                                                 CSRC / "alt_corr_bwd.hip"]

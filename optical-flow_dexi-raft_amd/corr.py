@@ -868,8 +868,22 @@ class AlternateCorrBlock:
     fly form's bit for bit (``coarse_first_level`` None: no volumes).  As in the
     reference, the constructor pools ``num_levels`` times, so fmaps smaller than
     2^num_levels in either dimension raise (core/corr.py:69-71).
-    bfloat16 and float16 fmaps are widened exactly to float32 first (the
-    reference's own cast, core/raft.py:139-142).
+    bfloat16 fmaps are widened exactly to float32 first (the reference's own
+    cast, core/raft.py:139-142).  float16 fmaps — what the encoders emit under
+    ``--mixed_precision`` — are read in place (``NATIVE_F16``; D % 16 == 0,
+    D <= 256, radius <= 6): the block keeps fmap1 and fmap2 level 0 as float16
+    NHWC (a free view of channels-last fmaps), pools level 1 from a transient
+    float32 copy of level 0 and the further levels from float32 as ever, and its
+    lookups pass ``DXR_ALT_IN_F16``: level 0 is one f16 matrix-core product per k
+    step on the raw values, the pooled levels two instead of three.  With finite
+    fmaps every output equals (``torch.equal``) that of the block built on
+    ``fmap1.float(), fmap2.float()``, under every ``out_dtype`` /
+    ``memory_format`` and with or without coarse volumes (those are computed once
+    from a transient float32 fmap1, unchanged); the block then holds no float32
+    copy of the fmaps.  With ``NATIVE_F16 = False``, for other D or radius, or if
+    the library declines the flag (``DXR_EUNSUPPORTED``: the operands are widened
+    once and the block goes on as before), float16 fmaps are widened like
+    bfloat16 ones.
 
     ``out_dtype`` (None / torch.float32, torch.float16, torch.bfloat16) and
     ``memory_format`` (None / torch.contiguous_format, torch.channels_last) are
@@ -902,6 +916,10 @@ class AlternateCorrBlock:
     # bit-identical, 6 % faster isolated, but 1.2 % slower in the 1080p step (r6u: 563 vs 570
     # pairs/s, two rounds each on one box), so off.
     COARSE_VOLUME_PLANES = False
+    # float16 fmaps are read in place (DXR_ALT_IN_F16; class docstring).  False: they are
+    # widened in the constructor like bfloat16 ones — the same outputs from float32 copies
+    # (scripts/ab_alt_f16.py compares the two; profiles/r14/alt_f16).
+    NATIVE_F16 = True
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, out_dtype=None,
                  memory_format=None):
@@ -914,7 +932,13 @@ class AlternateCorrBlock:
         B, D, H, W = _fmap_geometry(fmap1, fmap2)
         _require_no_grad(fmap1, fmap2, what="AlternateCorrBlock (the reference's alt_cuda_corr "
                                             "output carries no autograd graph, core/corr.py:85-88)")
-        if fmap1.dtype in (torch.bfloat16, torch.float16):
+        # float16 fmaps in place: until the library declines DXR_ALT_IN_F16
+        self._in16 = bool(self.NATIVE_F16 and fmap1.dtype == torch.float16 and
+                          isinstance(radius, int) and 0 <= radius <= 6 and
+                          D % 16 == 0 and D <= 256)
+        if self._in16:
+            pass   # kept as they are
+        elif fmap1.dtype in (torch.bfloat16, torch.float16):
             # The reference computes in float32 (core/raft.py:139-142 casts the
             # fmaps; alt_cuda_corr is float-only): bf16 / f16 encoder outputs are
             # widened exactly, keeping their memory format (channels-last stays a
@@ -934,12 +958,18 @@ class AlternateCorrBlock:
         # block): a free view of channels-last fmaps, one tiled transpose otherwise.
         # Only full-res fmap1 and the pooled fmap2 levels are used (core/corr.py:82-83),
         # so only those are pooled; ``pyramid`` materialises the rest on demand.
-        self._fmaps = (fmap1, fmap2)
+        # (float16 in place: no reference to the caller's fmaps; ``pyramid`` widens the
+        # NHWC operands into tensors of the caller's memory formats)
+        self._fmaps = None if self._in16 else (fmap1, fmap2)
+        self._fmaps_cl = (_channels_last(fmap1), _channels_last(fmap2))
         self._pyramid = None
         self._f1_nhwc = _nhwc(fmap1)
         self._f2_nhwc = [_nhwc(fmap2)]
-        for _ in range(1, num_levels):
-            self._f2_nhwc.append(_pool_nhwc(self._f2_nhwc[-1]))
+        for l in range(1, num_levels):
+            # (float16 level 0: level 1 is pooled from a transient float32 copy, bit for bit
+            # the widened block's; the means are not float16 numbers and stay float32)
+            above = self._f2_nhwc[-1]
+            self._f2_nhwc.append(_pool_nhwc(above.float() if l == 1 and self._in16 else above))
         self._f2_ptrs = (ctypes.c_void_p * num_levels)(*[t.data_ptr() for t in self._f2_nhwc])
         self.coarse_first_level = None
         self._volumes = None
@@ -975,8 +1005,11 @@ class AlternateCorrBlock:
         nbytes = (lib.dxr_alt_coarse_volumes_ws_bytes(B, H, W, D, self.num_levels, first)
                   if self.COARSE_VOLUME_PLANES else 0)
         ws = torch.empty(max(nbytes, 0), dtype=torch.uint8, device=self._device)
+        # (float16 in place: the volume GEMM reads a transient float32 fmap1 and the float32
+        # pooled levels >= first >= 1 — the widened block's call, bit for bit)
+        f1 = self._f1_nhwc.float() if self._in16 else self._f1_nhwc
         with _Launch(self._device):
-            st = lib.dxr_alt_coarse_volumes_ws(self._f1_nhwc.data_ptr(), self._f2_ptrs, B, H, W, D,
+            st = lib.dxr_alt_coarse_volumes_ws(f1.data_ptr(), self._f2_ptrs, B, H, W, D,
                                                self.num_levels, first, vol.data_ptr(), nat.ptr(ws),
                                                max(nbytes, 0), nat.stream_of(vol))
         nat.check(st, "AlternateCorrBlock coarse volumes (dxr_alt_coarse_volumes_ws)")
@@ -993,13 +1026,18 @@ class AlternateCorrBlock:
         — the lookup needs only full-res fmap1 and fmap2's first num_levels levels.
         """
         if self._pyramid is None:
-            p1 = [self._f1_nhwc]
+            p1 = [self._f1_nhwc.float()]   # (a no-op on float32 operands)
             p2 = list(self._f2_nhwc)
+            p2[0] = p2[0].float()
             while len(p1) < self.num_levels + 1:
                 p1.append(_pool_nhwc(p1[-1]))
             while len(p2) < self.num_levels + 1:
                 p2.append(_pool_nhwc(p2[-1]))
-            pyr = [self._fmaps]
+            fmaps = self._fmaps
+            if fmaps is None:   # float16 fmaps read in place: widened here, on first access
+                fmaps = tuple(t.permute(0, 3, 1, 2) if cl else t.permute(0, 3, 1, 2).contiguous()
+                              for t, cl in zip((p1[0], p2[0]), self._fmaps_cl))
+            pyr = [fmaps]
             pyr += [(a.permute(0, 3, 1, 2), b.permute(0, 3, 1, 2)) for a, b in zip(p1[1:], p2[1:])]
             self._pyramid = pyr
         return self._pyramid
@@ -1022,6 +1060,14 @@ class AlternateCorrBlock:
                 out = out.contiguous(memory_format=torch.channels_last)
         return out
 
+    def _widen_operands(self):
+        """The library declined ``DXR_ALT_IN_F16``: float32 operands from here on,
+        as the constructor makes them with ``NATIVE_F16 = False``."""
+        self._in16 = False
+        self._f1_nhwc = self._f1_nhwc.float()
+        self._f2_nhwc[0] = self._f2_nhwc[0].float()
+        self._f2_ptrs = (ctypes.c_void_p * self.num_levels)(*[t.data_ptr() for t in self._f2_nhwc])
+
     def _launch_lookup(self, c, flags):
         """One lookup with output ``flags`` or-ed onto the radius; None when the
         library declines a flagged request (``DXR_EUNSUPPORTED``)."""
@@ -1033,7 +1079,7 @@ class AlternateCorrBlock:
         else:
             out = torch.empty((B, self.num_levels * rd * rd, H, W), dtype=torch.float32,
                               device=self._device)
-        radius = self.radius | flags
+        radius = self.radius | flags | (nat.DXR_ALT_IN_F16 if self._in16 else 0)
         lib = nat.load()
         first = self.coarse_first_level
         if first is None:
@@ -1046,6 +1092,9 @@ class AlternateCorrBlock:
                                                 c.data_ptr(), out.data_ptr(), B, H, W, D,
                                                 self.num_levels, radius, _sqrt_dim(D),
                                                 nat.ptr(ws), max(nbytes, 0), nat.stream_of(c))
+            if self._in16 and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
+                self._widen_operands()   # once: remembered, as a declined output flag is
+                return self._launch_lookup(c, flags)
             if flags and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
                 return None
             nat.check(st, "AlternateCorrBlock lookup (dxr_alt_corr_lookup_ws)")
@@ -1059,11 +1108,15 @@ class AlternateCorrBlock:
                                                        self.num_levels, first, radius,
                                                        _sqrt_dim(D), nat.ptr(ws), max(nbytes, 0),
                                                        nat.stream_of(c))
+                if self._in16 and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
+                    self._widen_operands()
+                    return self._launch_lookup(c, flags)
                 if flags and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
                     return None
                 nat.check(st, "AlternateCorrBlock lookup (dxr_alt_corr_lookup_levels_ws)")
+            # (the volumes are float32 whatever the fmaps: no input flag there)
             st = lib.dxr_alt_volume_lookup(self._volumes.data_ptr(), c.data_ptr(), out.data_ptr(),
-                                           B, H, W, self.num_levels, first, radius,
+                                           B, H, W, self.num_levels, first, self.radius | flags,
                                            _sqrt_dim(D), nat.stream_of(c))
         nat.check(st, "AlternateCorrBlock lookup (dxr_alt_volume_lookup)")
         return out

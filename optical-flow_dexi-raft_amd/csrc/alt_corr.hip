@@ -29,6 +29,12 @@
 #include "dxr_common.h"
 #include "out_store.h"
 
+// alt_corr_out.hip and alt_corr_in16.hip include this file for the lookup's
+// flagged forms only.
+#if defined(DXR_ALT_OUT_TU) || defined(DXR_ALT_IN16_TU)
+#define DXR_ALT_LOOKUP_TU
+#endif
+
 namespace {
 
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -51,6 +57,7 @@ struct AltGeom {
   long long coord_zstride, coord_cstride, coord_qstride;
   AltLevel lv[8];
   dxr::LevelLayout vlay{};  // FULL: the volume's paged level layout (offset from the volume buffer)
+  unsigned f16_levels = 0;  // IN16: bit l set: lv[l].f2 points at float16 cells
 };
 
 template <int R>
@@ -284,8 +291,22 @@ __device__ __forceinline__ void alt_split8h(const float (&x)[8], uint4& h, uint4
 // (DXR_OUT_NHWC: element (z, ch, q) at (z N + q) cout + ch).  Everything up to
 // the bilinear combination is the float32 NCHW form's code; without OUTX `okind`
 // is not read and the kernel is the one it was.
+// IN16 (alt_corr_in16.hip only; DXR_ALT_IN_F16): `f1` points at float16 rows and
+// so do the levels of g.f16_levels (level 0: the encoder's own map; the pooled
+// levels are means of four values, not float16 numbers, and stay float32).  A
+// float16 value's f16 pair is (its own bits, 0), so the query rows are copied
+// raw into one LDS plane (no split, NPL = 1) and
+//   - a float16 level's 16-byte cell load is the A operand itself: one product
+//     per k step (th qh), no fallback (IEEE arithmetic on the raw values);
+//   - a float32 level splits its cells as ever and issues two (tl qh, th qh);
+//     th ql multiplied by zero.  Its fallback widens the query row in registers.
+// The products kept are issued in the float32 form's k order, so with finite
+// fmaps every sum is the one the float32 form gives on the widened values
+// (dropped MFMAs added exact zeros; only a zero's sign can differ).  The level is
+// blockIdx.y: the branch is uniform per workgroup.  Without IN16 the kernel is
+// the one it was.
 template <int R, int NRB, int CMAX, bool H2 = false, int MINW = 2, bool BIN = false, int PF = 1,
-          int DMA = 0, int XP = 0, bool FULL = false, bool OUTX = false>
+          int DMA = 0, int XP = 0, bool FULL = false, bool OUTX = false, bool IN16 = false>
 __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* __restrict__ f1,
                                                                const float* __restrict__ coords,
                                                                float* __restrict__ out,
@@ -294,11 +315,16 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
                                                                long long ord_stride, int XL,
                                                                int okind) {
   static_assert(!OUTX || (!FULL && XP == 0), "flagged outputs: the product lookup only");
+  static_assert(!IN16 || (H2 && !FULL && XP == 0 && DMA == 0), "float16 fmaps: the product lookup only");
   constexpr int RD = 2 * R + 1, RD1 = RD + 1, NCELL = RD1 * RD1;
   constexpr int CHUNK = 4 * 32 * NRB;                       // box cells per chunk
   constexpr int KB = CMAX / 8;                              // 8-channel blocks
-  constexpr int NPL = H2 ? 2 : 3;                           // query operand planes
-  __shared__ __attribute__((aligned(16))) uint4 qplanes[NPL * KB * TQ]; // [plane][kb][q]
+  constexpr int NPL = IN16 ? 1 : H2 ? 2 : 3;                // query operand planes
+  // (IN16 with OUTX: at least the channels-last stage of the last phase, which one
+  // plane does not hold from r = 6)
+  constexpr int QPU = (IN16 && OUTX && TQ * (RD * RD | 1) * 4 > NPL * KB * TQ * 16)
+                          ? (TQ * (RD * RD | 1) * 4 + 15) / 16 : NPL * KB * TQ;
+  __shared__ __attribute__((aligned(16))) uint4 qplanes[QPU];           // [plane][kb][q]
   // window dot products, row pitch SP: odd (round 6), so the 32 lanes of a
   // half-wave reading S[q * SP + cell] for 32 queries hit 32 banks (pitch 100:
   // 4 q mod 32, a 4-way conflict on every phase-2 read).  XP bit 4: the old pitch.
@@ -342,6 +368,10 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
   const float* cz = coords + (long long)z * g.coord_zstride;
   const float* f1b = f1 + (long long)bf * g.f1_bstride;
   const float* f2b = lv.f2 + (long long)bf * lv.H2 * lv.W2 * g.C;
+  // IN16: the float16 views of the same operands; lvh: this level's cells are float16
+  const _Float16* f1h = reinterpret_cast<const _Float16*>(f1) + (long long)bf * g.f1_bstride;
+  const _Float16* f2h = reinterpret_cast<const _Float16*>(lv.f2) + (long long)bf * lv.H2 * lv.W2 * g.C;
+  const bool lvh = IN16 && ((g.f16_levels >> lvl) & 1u) != 0;
   const int H1 = g.N / W1;
   const int nkb = g.C / 8;
   // query of lane/slot qq: a pixel of the 4 x 8 tile, or (BIN) entry tile*32 + qq of
@@ -425,6 +455,10 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
       const int qy = min(ty * TQY + qq / TQX, H1 - 1), qx = min(tx * TQX + qq % TQX, W1 - 1);
       qsrc0 = qy * W1 + qx;
     }
+    if constexpr (IN16) {   // the float16 row is the operand
+      qplanes[kb * TQ + qq] = *reinterpret_cast<const uint4*>(f1h + (long long)qsrc0 * g.C + kb * 8);
+      continue;
+    }
     const float* src = f1b + (long long)qsrc0 * g.C + kb * 8;
     const float4 a = *reinterpret_cast<const float4*>(src);
     const float4 c = *reinterpret_cast<const float4*>(src + 4);
@@ -459,12 +493,14 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
   for (int c0 = 0; c0 < ncells; c0 += CHUNK) {
     af16 acc[NRB];
     const float* src[NRB];
+    const _Float16* srch[NRB];   // IN16, a float16 level
 #pragma unroll
     for (int rb = 0; rb < NRB; ++rb) {
       // A operand lane -> cell c0 + 32 (wave NRB + rb) + j, channels 8 kh .. + 8 per k16
       const int c = min(c0 + (wave * NRB + rb) * 32 + j, ncells - 1);
       const int cy = divbw(c), cx = c - cy * bw;
       src[rb] = f2b + ((long long)(by0 + cy) * lv.W2 + bx0 + cx) * g.C + 8 * kh;
+      if constexpr (IN16) srch[rb] = f2h + ((long long)(by0 + cy) * lv.W2 + bx0 + cx) * g.C + 8 * kh;
       if constexpr ((XP & 4) != 0) src[rb] = f2b + (long long)(j & 7) * g.C + 8 * kh;   // ablation: 8 hot cells
     }
     // DMA (f16 pair form): the wave's 32 cell vectors move by LDS-DMA, two k steps (128 B per cell)
@@ -622,6 +658,7 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
         fq = fqy * W1 + fqx;
       }
       const float* qsrc = f1b + (long long)fq * g.C + 8 * kh;
+      const _Float16* qsrch = f1h + (long long)fq * g.C + 8 * kh;
       for (int ks0 = 0; ks0 < nst; ks0 += PF)
 #pragma unroll
       for (int u = 0; u < PF; ++u) {
@@ -642,7 +679,8 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
         }
         if constexpr (M2) {
           const ah8 qh = __builtin_bit_cast(ah8, qplanes[(0 * KB + 2 * ks + kh) * TQ + j]);
-          const ah8 ql = __builtin_bit_cast(ah8, qplanes[(1 * KB + 2 * ks + kh) * TQ + j]);
+          // (IN16: no low plane — it would be zero — and no th ql product)
+          const ah8 ql = __builtin_bit_cast(ah8, qplanes[((IN16 ? 0 : 1) * KB + 2 * ks + kh) * TQ + j]);
 #pragma unroll
           for (int rb = 0; rb < NRB; ++rb) {
             const float4 a = ca[rb], b = cb[rb];
@@ -659,13 +697,23 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
               acc[rb][0] += __uint_as_float(h.x ^ l.y) + (float)qh[0] + (float)ql[1];
             } else {
             acc2[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh, acc2[rb], 0, 0, 0);
-            acc2[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql, acc2[rb], 0, 0, 0);
+            if constexpr (!IN16)
+              acc2[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql, acc2[rb], 0, 0, 0);
             acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, qh, acc[rb], 0, 0, 0);
             }
           }
         } else {
           abf8 qh, qm, ql;
-          if constexpr (H2) {     // fallback: split the query operand here
+          if constexpr (H2 && IN16) {   // fallback: the float16 query row, widened here
+            const ah8 u = *reinterpret_cast<const ah8*>(qsrch + ks * 16);
+            const float x[8] = {(float)u[0], (float)u[1], (float)u[2], (float)u[3],
+                                (float)u[4], (float)u[5], (float)u[6], (float)u[7]};
+            uint4 h, m, l;
+            alt_split8(x, h, m, l);
+            qh = __builtin_bit_cast(abf8, h);
+            qm = __builtin_bit_cast(abf8, m);
+            ql = __builtin_bit_cast(abf8, l);
+          } else if constexpr (H2) {     // fallback: split the query operand here
             const float4 u = *reinterpret_cast<const float4*>(qsrc + ks * 16);
             const float4 w = *reinterpret_cast<const float4*>(qsrc + ks * 16 + 4);
             const float x[8] = {u.x, u.y, u.z, u.w, w.x, w.y, w.z, w.w};
@@ -704,7 +752,55 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
           for (int r = 0; r < 16; ++r) acc[rb][r] = __builtin_fmaf(acc2[rb][r], 0x1p-11f, acc[rb][r]);
       }
     };
-    if constexpr (H2) {
+    // IN16, a float16 level: the cell vector's 16 bytes are the A operand; PF k
+    // steps in flight, one product per step, nothing to fall back to
+    auto kloop_h = [&]() {
+#pragma unroll
+      for (int rb = 0; rb < NRB; ++rb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[rb][r] = 0.f;
+      const int nst = nkb / 2;
+      uint4 rh[PF][NRB];
+#pragma unroll
+      for (int u = 0; u < PF; ++u)
+        if (u < nst) {
+#pragma unroll
+          for (int rb = 0; rb < NRB; ++rb)
+            rh[u][rb] = *reinterpret_cast<const uint4*>(srch[rb] + u * 16);
+        }
+      for (int ks0 = 0; ks0 < nst; ks0 += PF)
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        const int ks = ks0 + u;
+        if (ks >= nst) break;
+        uint4 ch[NRB];
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb) ch[rb] = rh[u][rb];
+        if (ks + PF < nst) {
+#pragma unroll
+          for (int rb = 0; rb < NRB; ++rb)
+            rh[u][rb] = *reinterpret_cast<const uint4*>(srch[rb] + (ks + PF) * 16);
+        }
+        const ah8 qh = __builtin_bit_cast(ah8, qplanes[(2 * ks + kh) * TQ + j]);
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb)
+          acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(ah8, ch[rb]), qh,
+                                                           acc[rb], 0, 0, 0);
+      }
+    };
+    if constexpr (IN16) {
+      if (lvh) {   // workgroup-uniform
+        kloop_h();
+      } else {
+        kloop(std::integral_constant<bool, true>{});
+        bool bad = false;
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) bad |= !(__builtin_fabsf(acc[rb][r]) <= 3.40282347e38f);
+        if (__ballot(bad) != 0) kloop(std::integral_constant<bool, false>{});   // wave-uniform
+      }
+    } else if constexpr (H2) {
       if constexpr (DMA == 2 && NRB == 1) {
         if (nkb % 2 == 0) kloop_dma2();
         else kloop(std::integral_constant<bool, true>{});
@@ -1163,9 +1259,15 @@ long long alt_order_bytes(long long H, long long W) {
 // A/B); from r = 6 the window buffers and index registers do not fit that bound
 // (hipcc: "desired occupancy 3, final 2"), so those radii ask for 2.
 constexpr int alt_minw(int r) { return r >= 6 ? 2 : 3; }
+// The float16-operand form (IN16): one query plane, 16 KB of LDS less per
+// workgroup, so one workgroup more per CU fits (hipcc, ordered form: r <= 5 128
+// VGPRs, 18-36 KB LDS, occupancy 4; r = 6 138 VGPRs, 42.5 KB, occupancy 3; no
+// scratch, no spills.  Asking for 5 spills 24-25 VGPRs.  DESIGN.md §3.17).
+constexpr int alt_minw16(int r) { return r >= 6 ? 3 : 4; }
 
 // OUTX / okind: the flagged output forms (alt_corr_mfma_kernel), tile order and ordered.
-template <int R, int NRB, int DMA = 0, int PF = 4, int XP = 0, bool OUTX = false>
+// IN16: float16 fmap1 and the float16 levels of g.f16_levels (alt_corr_in16.hip).
+template <int R, int NRB, int DMA = 0, int PF = 4, int XP = 0, bool OUTX = false, bool IN16 = false>
 int launch_alt_mfma_r(const float* f1, const float* coords, float* out, const AltGeom& g,
                       int levels, int Z, int W1, hipStream_t stream, void* ws = nullptr,
                       int xl = -1, int okind = 0) {
@@ -1211,12 +1313,20 @@ int launch_alt_mfma_r(const float* f1, const float* coords, float* out, const Al
       hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, 2, true, 1, DMA>), grid,
                          dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x,
                          reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL, 0);
+    else if constexpr (IN16)
+      hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw16(R), true, PF, 0, 0, false, OUTX, true>),
+                         grid, dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x,
+                         reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL, okind);
     else
       hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw(R), true, PF, 0, XP, false, OUTX>),
                          grid, dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x,
                          reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL, okind);
     return dxr::launch_status();
   }
+  if constexpr (IN16)
+    hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw16(R), false, 1, 0, 0, false, OUTX, true>), grid,
+                       dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x, nullptr, 0, 0, okind);
+  else
   hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw(R), false, 1, 0, 0, false, OUTX>), grid,
                      dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x, nullptr, 0, 0, okind);
   return dxr::launch_status();
@@ -1236,7 +1346,8 @@ int launch_alt_r(const float* f1, const float* coords, float* out, const AltGeom
 // OUTX / okind: a flagged request (alt_corr_out.hip).  The MFMA forms implement
 // every flag combination; the VALU forms decline (DXR_EUNSUPPORTED, nothing
 // launched): a caller runs the unflagged call and converts.
-template <bool OUTX = false>
+// IN16: float16 operands (alt_corr_in16.hip); the MFMA forms only, as the flags.
+template <bool OUTX = false, bool IN16 = false>
 int launch_alt(const float* f1, const float* coords, float* out, const AltGeom& g, int levels,
                int Z, int radius, bool vec, hipStream_t stream, int W1 = 0,
                void* ord = nullptr, int okind = 0) {
@@ -1246,8 +1357,8 @@ int launch_alt(const float* f1, const float* coords, float* out, const AltGeom& 
   if (vec && W1 > 0 && g.C % 16 == 0 && g.C <= 256) {
 #define DXR_ALT_MFMA(RR)                                                                       \
   case RR:                                                                                     \
-    return launch_alt_mfma_r<RR, 1, 0, 4, 0, OUTX>(f1, coords, out, g, levels, Z, W1, stream, \
-                                                   ord, -1, okind);
+    return launch_alt_mfma_r<RR, 1, 0, 4, 0, OUTX, IN16>(f1, coords, out, g, levels, Z, W1,    \
+                                                         stream, ord, -1, okind);
     switch (radius) {
       DXR_ALT_MFMA(0)
       DXR_ALT_MFMA(1)
@@ -1260,7 +1371,7 @@ int launch_alt(const float* f1, const float* coords, float* out, const AltGeom& 
     }
 #undef DXR_ALT_MFMA
   }
-  if constexpr (OUTX) return DXR_EUNSUPPORTED;
+  if constexpr (OUTX || IN16) return DXR_EUNSUPPORTED;
   switch (radius) {
     case 0: return launch_alt_r<0>(f1, coords, out, g, levels, Z, vec, stream);
     case 1: return launch_alt_r<1>(f1, coords, out, g, levels, Z, vec, stream);
@@ -1282,7 +1393,7 @@ float pow2_recip(float d) {
   return (m == 0.5f && e > -125 && e < 126) ? 1.f / d : 0.f;
 }
 
-#ifndef DXR_ALT_OUT_TU   // alt_corr_out.hip takes the lookup's flagged forms only
+#ifndef DXR_ALT_LOOKUP_TU   // alt_corr_out.hip / alt_corr_in16.hip take the lookup's flagged forms only
 // ---------------------------------------------------------------------------
 // alt_cuda_corr.backward, reference-FFI form (correlation_kernel.cu:122-256,
 // launched by :288-320).  For query q of pair b and coordinate set n, cell
@@ -1494,11 +1605,11 @@ __global__ __launch_bounds__(256) void avg_pool2x2_nhwc_kernel(const float* __re
   }
 }
 
-#endif  // DXR_ALT_OUT_TU
+#endif  // DXR_ALT_LOOKUP_TU
 
 }  // namespace
 
-#ifndef DXR_ALT_OUT_TU
+#ifndef DXR_ALT_LOOKUP_TU
 extern "C" int dxr_alt_corr_forward(const float* fmap1, const float* fmap2, const float* coords,
                                     float* corr, int64_t B, int64_t H1, int64_t W1, int64_t H2,
                                     int64_t W2, int64_t C, int64_t Nc, int radius,
@@ -1607,13 +1718,14 @@ extern "C" int dxr_avg_pool2x2_nhwc(const float* in, float* out, int64_t B, int6
   return dxr::launch_status();
 }
 
-#endif  // DXR_ALT_OUT_TU
+#endif  // DXR_ALT_LOOKUP_TU
 
 namespace {
 // n_levels < 0: every level; else only levels [0, n_levels) of a num_levels-level
 // output (the rest come from dxr_alt_volume_lookup).
 // OUTX / okind: a flagged request (launch_alt); `out` then holds what okind says.
-template <bool OUTX = false>
+// IN16: DXR_ALT_IN_F16 — fmap1 and fmap2_levels[0] point at float16.
+template <bool OUTX = false, bool IN16 = false>
 int alt_lookup(const float* fmap1, const float* const* fmap2_levels, const float* coords, float* out,
                int64_t B, int64_t H, int64_t W, int64_t C, int num_levels, int radius,
                float divisor, void* workspace, int64_t workspace_bytes, hipStream_t stream,
@@ -1645,14 +1757,35 @@ int alt_lookup(const float* fmap1, const float* const* fmap2_levels, const float
     vec = vec && aligned16(fmap2_levels[l]);
     g.lv[l] = AltLevel{fmap2_levels[l], L.h[l], L.w[l], 1.f / (float)(1 << l), l * rd * rd};
   }
+  if constexpr (IN16) g.f16_levels = 1u;
   void* ord = nullptr;
   if (workspace != nullptr && aligned16(workspace) &&
       workspace_bytes >= (long long)B * nl * alt_order_bytes(H, W))
     ord = workspace;
-  return launch_alt<OUTX>(fmap1, coords, out, g, nl, (int)B, radius, vec, stream, (int)W, ord, okind);
+  return launch_alt<OUTX, IN16>(fmap1, coords, out, g, nl, (int)B, radius, vec, stream, (int)W, ord,
+                                okind);
 }
 
-#ifdef DXR_ALT_OUT_TU
+#if defined(DXR_ALT_IN16_TU)
+}  // namespace
+
+// alt_corr_in16.hip: this file's lookup on float16 fmaps (DXR_ALT_IN_F16), with
+// and without output flags, and nothing else of it.
+int dxr::alt_lookup_in16(const void* fmap1, const void* const* fmap2_levels, const float* coords,
+                         void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W,
+                         int64_t C, int num_levels, int radius, float divisor, void* workspace,
+                         int64_t workspace_bytes, hipStream_t stream, int n_levels) {
+  const int okind = (out_flag == DXR_OUT_F16 ? 1 : 0) | (out_flag == DXR_OUT_BF16 ? 2 : 0) |
+                    (nhwc ? 4 : 0);
+  const float* f1 = static_cast<const float*>(fmap1);
+  const float* const* f2 = reinterpret_cast<const float* const*>(fmap2_levels);
+  if (okind == 0)
+    return alt_lookup<false, true>(f1, f2, coords, static_cast<float*>(out), B, H, W, C, num_levels,
+                                   radius, divisor, workspace, workspace_bytes, stream, n_levels, 0);
+  return alt_lookup<true, true>(f1, f2, coords, static_cast<float*>(out), B, H, W, C, num_levels,
+                                radius, divisor, workspace, workspace_bytes, stream, n_levels, okind);
+}
+#elif defined(DXR_ALT_OUT_TU)
 }  // namespace
 
 // alt_corr_out.hip: this file's lookup with the flagged output forms, and nothing
@@ -2150,8 +2283,14 @@ int alt_lookup_entry(const float* fmap1, const float* const* fmap2_levels, const
   if (radius >= 0) {
     int out_flag;
     bool nhwc;
+    const bool in16 = (radius & DXR_ALT_IN_F16) != 0;
+    radius &= ~DXR_ALT_IN_F16;
     if (!dxr::split_out_flags(&radius, &out_flag, &nhwc)) return DXR_EINVAL;
     if (out_flag != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return DXR_EINVAL;
+    if (in16)   // float16 fmap1 and level 0, with or without output flags
+      return dxr::alt_lookup_in16(fmap1, reinterpret_cast<const void* const*>(fmap2_levels), coords,
+                                  out, out_flag, nhwc, B, H, W, C, num_levels, radius, divisor,
+                                  workspace, workspace_bytes, stream, n_levels);
     if (out_flag != 0 || nhwc)
       return dxr::alt_lookup_out(fmap1, fmap2_levels, coords, out, out_flag, nhwc, B, H, W, C,
                                  num_levels, radius, divisor, workspace, workspace_bytes, stream,
@@ -2191,7 +2330,7 @@ extern "C" int dxr_alt_corr_lookup_levels_ws(const float* fmap1, const float* co
                                              int radius, float divisor, void* workspace,
                                              int64_t workspace_bytes, hipStream_t stream) {
   {   // invalid output flags answer first, as in the other lookups
-    int r = radius, f;
+    int r = radius & ~DXR_ALT_IN_F16, f;
     bool n;
     if (radius >= 0 && !dxr::split_out_flags(&r, &f, &n)) return DXR_EINVAL;
   }
@@ -2199,5 +2338,4 @@ extern "C" int dxr_alt_corr_lookup_levels_ws(const float* fmap1, const float* co
   return alt_lookup_entry(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
                           workspace, workspace_bytes, stream, n_levels);
 }
-#endif  // DXR_ALT_OUT_TU
-
+#endif  // DXR_ALT_IN16_TU / DXR_ALT_OUT_TU

@@ -65,6 +65,15 @@ int alt_lookup_out(const float* fmap1, const float* const* fmap2_levels, const f
                    void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W, int64_t C,
                    int num_levels, int radius, float divisor, void* workspace,
                    int64_t workspace_bytes, hipStream_t stream, int n_levels);
+// The same three lookups with DXR_ALT_IN_F16 on `radius` (split off by the entry
+// points, like the output flags, any of which may come with it: out_flag 0 /
+// DXR_OUT_F16 / DXR_OUT_BF16, nhwc): fmap1 and fmap2_levels[0] point at float16,
+// the further levels at float32.  Defined in alt_corr_in16.hip, the only
+// translation unit that instantiates the float16-operand forms.
+int alt_lookup_in16(const void* fmap1, const void* const* fmap2_levels, const float* coords,
+                    void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W, int64_t C,
+                    int num_levels, int radius, float divisor, void* workspace,
+                    int64_t workspace_bytes, hipStream_t stream, int n_levels);
 // dxr_alt_corr_backward with DXR_ALT_BWD_ACCUMULATE on `radius` (passed whole; B,
 // the map sizes and C already checked positive, radius >= 0): validation and
 // the MFMA kernel that adds into both gradients.  Defined in alt_corr_bwd.hip.
