@@ -159,6 +159,15 @@ enum dxr_dtype {
  */
 #define DXR_ALT_IN_F16 0x8000
 
+/*
+ * The same for bfloat16 maps, the usual autocast dtype: fmap1 and fmap2 level 0
+ * are read as bfloat16, without a float32 copy.  One input flag at a time: both
+ * together are DXR_EINVAL.  Semantics, served shapes and validation: "Bfloat16
+ * fmaps on radius" at dxr_alt_corr_lookup.  On any other entry point the bit is
+ * an unknown flag.
+ */
+#define DXR_ALT_IN_BF16 0x20000
+
 enum dxr_layout {
   DXR_NCHW = 0,         /* fmaps [B, D, H, W] (core/raft.py:139-142)              */
   DXR_NHWC = 1          /* fmaps [B, H, W, D] (channels-last encoders, §8(f) row 4) */
@@ -640,6 +649,33 @@ int dxr_alt_corr_backward(const float* fmap1, const float* fmap2,
  * and runs the unflagged call.  dxr_alt_volume_lookup (no fmaps),
  * dxr_alt_corr_forward / _backward and dxr_alt_coarse_volumes* do not take the
  * bit: there it is an unknown flag.
+ *
+ * Bfloat16 fmaps on radius.  DXR_ALT_IN_BF16, or-ed onto the `radius` of
+ * dxr_alt_corr_lookup, dxr_alt_corr_lookup_ws and dxr_alt_corr_lookup_levels_ws,
+ * alone or with any valid combination of the output flags above: fmap1 and
+ * fmap2_levels[0] point at [B, H, W, C] bfloat16 (through the float*
+ * parameters) — the maps an encoder emits under bfloat16 autocast, which the
+ * reference widens first (core/raft.py:139-142) — and fmap2_levels[l >= 1] at
+ * float32: the 2x2 means pooled from the widened level 0.  Level 0 is one bf16
+ * matrix-core product per k step on the raw values: 8-bit significands multiply
+ * exactly into the float32 accumulator and bfloat16 has float32's exponent
+ * range, so there is no split, no scaling and no overflow fallback.  A pooled
+ * level's float32 cells are split exactly into three bfloat16 parts, each
+ * multiplied with the raw query: three exact products per k step.  Every output
+ * is the float32 sum of exact products, within 1e-5 of sum |fmap1| |fmap2|
+ * (combined as the output is) of the exact result; it is not claimed bit-equal
+ * to the unflagged call on the widened maps, which accumulates the same
+ * products through another instruction and in its own fallback where a value
+ * lies outside float16's range.  inf / NaN propagate by IEEE arithmetic.  The
+ * ordered and tile-order forms agree bit for bit, and a flagged output is the
+ * float32 NCHW output converted.  DXR_ALT_IN_F16 | DXR_ALT_IN_BF16 is
+ * DXR_EINVAL.  Served when C % 16 == 0, C <= 256, radius <= 6 and fmap1 and
+ * every level are 16-byte aligned; any other C or alignment and radius > 6 are
+ * DXR_EUNSUPPORTED, null pointers DXR_EINVAL, B == 0 DXR_OK, all answered on the
+ * host before any launch; the caller widens and runs the unflagged call.
+ * dxr_alt_volume_lookup, dxr_alt_corr_forward / _backward and
+ * dxr_alt_coarse_volumes* do not take the bit, as they do not take
+ * DXR_ALT_IN_F16.
  */
 int dxr_alt_corr_lookup(const float* fmap1, const float* const* fmap2_levels,
                         const float* coords, float* out,

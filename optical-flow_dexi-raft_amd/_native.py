@@ -33,6 +33,8 @@ DXR_ALT_BWD_ACCUMULATE = 0x2000
 # input dtype flag of dxr_alt_corr_lookup / _ws / _levels_ws, or-ed onto their radius (with or
 # without output flags): fmap1 and fmap2 level 0 are float16, the pooled levels float32
 DXR_ALT_IN_F16 = 0x8000
+# the same for bfloat16 fmaps (one input flag at a time)
+DXR_ALT_IN_BF16 = 0x20000
 DXR_NCHW, DXR_NHWC = 0, 1
 DXR_BUILD_AUTO, DXR_BUILD_EXACT_F32 = 0, 1
 

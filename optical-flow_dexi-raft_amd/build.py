@@ -57,6 +57,7 @@ def _sources(experiments: bool = False) -> list[Path]:
                                                 CSRC / "corr_lookup_alt_out.hip",
                                                 CSRC / "alt_corr_out.hip",
                                                 CSRC / "alt_corr_in16.hip",
+                                                CSRC / "alt_corr_inbf16.hip",
                                                 # the accumulating backward xp_alt's copy of
                                                 # dxr_alt_corr_backward dispatches to
                                                 CSRC / "alt_corr_bwd.hip"]

@@ -868,8 +868,8 @@ class AlternateCorrBlock:
     fly form's bit for bit (``coarse_first_level`` None: no volumes).  As in the
     reference, the constructor pools ``num_levels`` times, so fmaps smaller than
     2^num_levels in either dimension raise (core/corr.py:69-71).
-    bfloat16 fmaps are widened exactly to float32 first (the reference's own
-    cast, core/raft.py:139-142).  float16 fmaps — what the encoders emit under
+    16-bit fmaps are read in place, where the reference widens them to float32
+    first (its own cast, core/raft.py:139-142).  float16 fmaps — what the encoders emit under
     ``--mixed_precision`` — are read in place (``NATIVE_F16``; D % 16 == 0,
     D <= 256, radius <= 6): the block keeps fmap1 and fmap2 level 0 as float16
     NHWC (a free view of channels-last fmaps), pools level 1 from a transient
@@ -882,8 +882,23 @@ class AlternateCorrBlock:
     from a transient float32 fmap1, unchanged); the block then holds no float32
     copy of the fmaps.  With ``NATIVE_F16 = False``, for other D or radius, or if
     the library declines the flag (``DXR_EUNSUPPORTED``: the operands are widened
-    once and the block goes on as before), float16 fmaps are widened like
-    bfloat16 ones.
+    once and the block goes on as before), float16 fmaps are widened exactly to
+    float32 in the constructor.
+    bfloat16 fmaps — the usual autocast dtype — are read in place in the same way
+    (``NATIVE_BF16``, the same D and radius; ``DXR_ALT_IN_BF16``): the same
+    bfloat16 NHWC operands, float32 pooled levels (bit for bit the widened
+    block's), transient float32 copies for level 1 and the coarse volumes (those
+    are the widened block's bit for bit), and the same fallbacks.  Level 0 is one
+    bf16 matrix-core product per k step on the raw values — exact products,
+    float32's exponent range: no split, no scaling, no overflow fallback — and a
+    pooled level three exact products (its float32 cells split three ways, times
+    the raw query).  Unlike the float16 form this one is not bit-equal to the
+    widened block: the same exact products are summed by another instruction (and
+    the widened block recomputes values outside float16's range on its fallback).
+    Every output is within 1e-5 of sum |fmap1| |fmap2| of the exact result (the
+    criterion of tests/test_gpu_alt_oracle.py), the ordered and tile-order forms
+    agree bit for bit, and every ``out_dtype`` / ``memory_format`` output is the
+    block's own float32 NCHW output converted.
 
     ``out_dtype`` (None / torch.float32, torch.float16, torch.bfloat16) and
     ``memory_format`` (None / torch.contiguous_format, torch.channels_last) are
@@ -920,6 +935,10 @@ class AlternateCorrBlock:
     # widened in the constructor like bfloat16 ones — the same outputs from float32 copies
     # (scripts/ab_alt_f16.py compares the two; profiles/r14/alt_f16).
     NATIVE_F16 = True
+    # bfloat16 fmaps are read in place (DXR_ALT_IN_BF16; class docstring).  False: they are
+    # widened in the constructor, call for call as before the flag existed
+    # (scripts/ab_alt_bf16.py compares the two; profiles/r15/alt_bf16).
+    NATIVE_BF16 = True
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, out_dtype=None,
                  memory_format=None):
@@ -932,11 +951,12 @@ class AlternateCorrBlock:
         B, D, H, W = _fmap_geometry(fmap1, fmap2)
         _require_no_grad(fmap1, fmap2, what="AlternateCorrBlock (the reference's alt_cuda_corr "
                                             "output carries no autograd graph, core/corr.py:85-88)")
-        # float16 fmaps in place: until the library declines DXR_ALT_IN_F16
-        self._in16 = bool(self.NATIVE_F16 and fmap1.dtype == torch.float16 and
-                          isinstance(radius, int) and 0 <= radius <= 6 and
-                          D % 16 == 0 and D <= 256)
-        if self._in16:
+        # 16-bit fmaps in place: until the library declines DXR_ALT_IN_F16 / DXR_ALT_IN_BF16
+        # (_in16: float16 operands; _inbf16: bfloat16 operands)
+        served = isinstance(radius, int) and 0 <= radius <= 6 and D % 16 == 0 and D <= 256
+        self._in16 = bool(self.NATIVE_F16 and fmap1.dtype == torch.float16 and served)
+        self._inbf16 = bool(self.NATIVE_BF16 and fmap1.dtype == torch.bfloat16 and served)
+        if self._in16 or self._inbf16:
             pass   # kept as they are
         elif fmap1.dtype in (torch.bfloat16, torch.float16):
             # The reference computes in float32 (core/raft.py:139-142 casts the
@@ -958,18 +978,18 @@ class AlternateCorrBlock:
         # block): a free view of channels-last fmaps, one tiled transpose otherwise.
         # Only full-res fmap1 and the pooled fmap2 levels are used (core/corr.py:82-83),
         # so only those are pooled; ``pyramid`` materialises the rest on demand.
-        # (float16 in place: no reference to the caller's fmaps; ``pyramid`` widens the
+        # (16-bit in place: no reference to the caller's fmaps; ``pyramid`` widens the
         # NHWC operands into tensors of the caller's memory formats)
-        self._fmaps = None if self._in16 else (fmap1, fmap2)
+        self._fmaps = None if self._in16 or self._inbf16 else (fmap1, fmap2)
         self._fmaps_cl = (_channels_last(fmap1), _channels_last(fmap2))
         self._pyramid = None
         self._f1_nhwc = _nhwc(fmap1)
         self._f2_nhwc = [_nhwc(fmap2)]
         for l in range(1, num_levels):
-            # (float16 level 0: level 1 is pooled from a transient float32 copy, bit for bit
-            # the widened block's; the means are not float16 numbers and stay float32)
+            # (16-bit level 0: level 1 is pooled from a transient float32 copy, bit for bit
+            # the widened block's; the means are not 16-bit numbers and stay float32)
             above = self._f2_nhwc[-1]
-            self._f2_nhwc.append(_pool_nhwc(above.float() if l == 1 and self._in16 else above))
+            self._f2_nhwc.append(_pool_nhwc(above.float() if l == 1 else above))
         self._f2_ptrs = (ctypes.c_void_p * num_levels)(*[t.data_ptr() for t in self._f2_nhwc])
         self.coarse_first_level = None
         self._volumes = None
@@ -1005,9 +1025,9 @@ class AlternateCorrBlock:
         nbytes = (lib.dxr_alt_coarse_volumes_ws_bytes(B, H, W, D, self.num_levels, first)
                   if self.COARSE_VOLUME_PLANES else 0)
         ws = torch.empty(max(nbytes, 0), dtype=torch.uint8, device=self._device)
-        # (float16 in place: the volume GEMM reads a transient float32 fmap1 and the float32
+        # (16-bit in place: the volume GEMM reads a transient float32 fmap1 and the float32
         # pooled levels >= first >= 1 — the widened block's call, bit for bit)
-        f1 = self._f1_nhwc.float() if self._in16 else self._f1_nhwc
+        f1 = self._f1_nhwc.float()   # (a no-op on float32 operands)
         with _Launch(self._device):
             st = lib.dxr_alt_coarse_volumes_ws(f1.data_ptr(), self._f2_ptrs, B, H, W, D,
                                                self.num_levels, first, vol.data_ptr(), nat.ptr(ws),
@@ -1034,7 +1054,7 @@ class AlternateCorrBlock:
             while len(p2) < self.num_levels + 1:
                 p2.append(_pool_nhwc(p2[-1]))
             fmaps = self._fmaps
-            if fmaps is None:   # float16 fmaps read in place: widened here, on first access
+            if fmaps is None:   # 16-bit fmaps read in place: widened here, on first access
                 fmaps = tuple(t.permute(0, 3, 1, 2) if cl else t.permute(0, 3, 1, 2).contiguous()
                               for t, cl in zip((p1[0], p2[0]), self._fmaps_cl))
             pyr = [fmaps]
@@ -1061,9 +1081,10 @@ class AlternateCorrBlock:
         return out
 
     def _widen_operands(self):
-        """The library declined ``DXR_ALT_IN_F16``: float32 operands from here on,
-        as the constructor makes them with ``NATIVE_F16 = False``."""
-        self._in16 = False
+        """The library declined ``DXR_ALT_IN_F16`` / ``DXR_ALT_IN_BF16``: float32
+        operands from here on, as the constructor makes them with ``NATIVE_F16`` /
+        ``NATIVE_BF16 = False``."""
+        self._in16 = self._inbf16 = False
         self._f1_nhwc = self._f1_nhwc.float()
         self._f2_nhwc[0] = self._f2_nhwc[0].float()
         self._f2_ptrs = (ctypes.c_void_p * self.num_levels)(*[t.data_ptr() for t in self._f2_nhwc])
@@ -1079,7 +1100,9 @@ class AlternateCorrBlock:
         else:
             out = torch.empty((B, self.num_levels * rd * rd, H, W), dtype=torch.float32,
                               device=self._device)
-        radius = self.radius | flags | (nat.DXR_ALT_IN_F16 if self._in16 else 0)
+        in_flag = (nat.DXR_ALT_IN_F16 if self._in16 else
+                   nat.DXR_ALT_IN_BF16 if self._inbf16 else 0)
+        radius = self.radius | flags | in_flag
         lib = nat.load()
         first = self.coarse_first_level
         if first is None:
@@ -1092,7 +1115,7 @@ class AlternateCorrBlock:
                                                 c.data_ptr(), out.data_ptr(), B, H, W, D,
                                                 self.num_levels, radius, _sqrt_dim(D),
                                                 nat.ptr(ws), max(nbytes, 0), nat.stream_of(c))
-            if self._in16 and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
+            if in_flag and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
                 self._widen_operands()   # once: remembered, as a declined output flag is
                 return self._launch_lookup(c, flags)
             if flags and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
@@ -1108,7 +1131,7 @@ class AlternateCorrBlock:
                                                        self.num_levels, first, radius,
                                                        _sqrt_dim(D), nat.ptr(ws), max(nbytes, 0),
                                                        nat.stream_of(c))
-                if self._in16 and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
+                if in_flag and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
                     self._widen_operands()
                     return self._launch_lookup(c, flags)
                 if flags and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:

@@ -29,9 +29,9 @@
 #include "dxr_common.h"
 #include "out_store.h"
 
-// alt_corr_out.hip and alt_corr_in16.hip include this file for the lookup's
-// flagged forms only.
-#if defined(DXR_ALT_OUT_TU) || defined(DXR_ALT_IN16_TU)
+// alt_corr_out.hip, alt_corr_in16.hip and alt_corr_inbf16.hip include this file
+// for the lookup's flagged forms only.
+#if defined(DXR_ALT_OUT_TU) || defined(DXR_ALT_IN16_TU) || defined(DXR_ALT_INBF16_TU)
 #define DXR_ALT_LOOKUP_TU
 #endif
 
@@ -57,7 +57,7 @@ struct AltGeom {
   long long coord_zstride, coord_cstride, coord_qstride;
   AltLevel lv[8];
   dxr::LevelLayout vlay{};  // FULL: the volume's paged level layout (offset from the volume buffer)
-  unsigned f16_levels = 0;  // IN16: bit l set: lv[l].f2 points at float16 cells
+  unsigned f16_levels = 0;  // IN16: bit l set: lv[l].f2 points at float16 (INBF: bfloat16) cells
 };
 
 template <int R>
@@ -305,8 +305,21 @@ __device__ __forceinline__ void alt_split8h(const float (&x)[8], uint4& h, uint4
 // (dropped MFMAs added exact zeros; only a zero's sign can differ).  The level is
 // blockIdx.y: the branch is uniform per workgroup.  Without IN16 the kernel is
 // the one it was.
+// INBF (alt_corr_inbf16.hip only; DXR_ALT_IN_BF16; with IN16, whose 16-bit
+// plumbing it shares: the raw query plane, the 16-byte cell loads, the ring):
+// the 16-bit values are bfloat16.  8-bit significands multiply exactly into the
+// f32 accumulator and bfloat16 has float32's exponent range, so nothing is split,
+// scaled or recomputed:
+//   - a bfloat16 level: one v_mfma_f32_32x32x16_bf16 per k step on the raw
+//     cell vector and the raw query;
+//   - a float32 level: its cells split three ways by alt_split8 (exact: 3 x 8
+//     bits), each part times the raw bfloat16 query — three exact products
+//     (tl q, tm q, th q: small terms first), no query parts; inf and NaN go
+//     through the split as in the float32 form's fallback, so no second pass.
+// Without INBF no statement of it is compiled.
 template <int R, int NRB, int CMAX, bool H2 = false, int MINW = 2, bool BIN = false, int PF = 1,
-          int DMA = 0, int XP = 0, bool FULL = false, bool OUTX = false, bool IN16 = false>
+          int DMA = 0, int XP = 0, bool FULL = false, bool OUTX = false, bool IN16 = false,
+          bool INBF = false>
 __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* __restrict__ f1,
                                                                const float* __restrict__ coords,
                                                                float* __restrict__ out,
@@ -316,6 +329,7 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
                                                                int okind) {
   static_assert(!OUTX || (!FULL && XP == 0), "flagged outputs: the product lookup only");
   static_assert(!IN16 || (H2 && !FULL && XP == 0 && DMA == 0), "float16 fmaps: the product lookup only");
+  static_assert(!INBF || IN16, "bfloat16 fmaps: a kind of the 16-bit operand form");
   constexpr int RD = 2 * R + 1, RD1 = RD + 1, NCELL = RD1 * RD1;
   constexpr int CHUNK = 4 * 32 * NRB;                       // box cells per chunk
   constexpr int KB = CMAX / 8;                              // 8-channel blocks
@@ -704,7 +718,9 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
           }
         } else {
           abf8 qh, qm, ql;
-          if constexpr (H2 && IN16) {   // fallback: the float16 query row, widened here
+          if constexpr (INBF) {   // the raw bfloat16 query row is the B operand of all three
+            qh = __builtin_bit_cast(abf8, qplanes[(2 * ks + kh) * TQ + j]);
+          } else if constexpr (H2 && IN16) {   // fallback: the float16 query row, widened here
             const ah8 u = *reinterpret_cast<const ah8*>(qsrch + ks * 16);
             const float x[8] = {(float)u[0], (float)u[1], (float)u[2], (float)u[3],
                                 (float)u[4], (float)u[5], (float)u[6], (float)u[7]};
@@ -735,6 +751,12 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
             alt_split8(x, h, m, l);
             const abf8 th = __builtin_bit_cast(abf8, h), tm = __builtin_bit_cast(abf8, m),
                        tl = __builtin_bit_cast(abf8, l);
+            if constexpr (INBF) {   // (q has no middle or low part)
+              acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tl, qh, acc[rb], 0, 0, 0);
+              acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tm, qh, acc[rb], 0, 0, 0);
+              acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(th, qh, acc[rb], 0, 0, 0);
+              continue;
+            }
             // small terms first
             acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tm, qm, acc[rb], 0, 0, 0);
             acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tl, qh, acc[rb], 0, 0, 0);
@@ -781,6 +803,14 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
           for (int rb = 0; rb < NRB; ++rb)
             rh[u][rb] = *reinterpret_cast<const uint4*>(srch[rb] + (ks + PF) * 16);
         }
+        if constexpr (INBF) {
+          const abf8 qb = __builtin_bit_cast(abf8, qplanes[(2 * ks + kh) * TQ + j]);
+#pragma unroll
+          for (int rb = 0; rb < NRB; ++rb)
+            acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(abf8, ch[rb]), qb,
+                                                              acc[rb], 0, 0, 0);
+          continue;
+        }
         const ah8 qh = __builtin_bit_cast(ah8, qplanes[(2 * ks + kh) * TQ + j]);
 #pragma unroll
         for (int rb = 0; rb < NRB; ++rb)
@@ -791,6 +821,8 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
     if constexpr (IN16) {
       if (lvh) {   // workgroup-uniform
         kloop_h();
+      } else if constexpr (INBF) {   // three exact bf16 products, one pass
+        kloop(std::integral_constant<bool, false>{});
       } else {
         kloop(std::integral_constant<bool, true>{});
         bool bad = false;
@@ -1264,10 +1296,15 @@ constexpr int alt_minw(int r) { return r >= 6 ? 2 : 3; }
 // VGPRs, 18-36 KB LDS, occupancy 4; r = 6 138 VGPRs, 42.5 KB, occupancy 3; no
 // scratch, no spills.  Asking for 5 spills 24-25 VGPRs.  DESIGN.md §3.17).
 constexpr int alt_minw16(int r) { return r >= 6 ? 3 : 4; }
+// The bfloat16-operand form (INBF) asks for the same bound (DESIGN.md §3.18 has
+// hipcc's figures per radius).
+constexpr int alt_minwbf(int r) { return r >= 6 ? 3 : 4; }
 
 // OUTX / okind: the flagged output forms (alt_corr_mfma_kernel), tile order and ordered.
 // IN16: float16 fmap1 and the float16 levels of g.f16_levels (alt_corr_in16.hip).
-template <int R, int NRB, int DMA = 0, int PF = 4, int XP = 0, bool OUTX = false, bool IN16 = false>
+// INBF (with IN16): they are bfloat16 (alt_corr_inbf16.hip).
+template <int R, int NRB, int DMA = 0, int PF = 4, int XP = 0, bool OUTX = false, bool IN16 = false,
+          bool INBF = false>
 int launch_alt_mfma_r(const float* f1, const float* coords, float* out, const AltGeom& g,
                       int levels, int Z, int W1, hipStream_t stream, void* ws = nullptr,
                       int xl = -1, int okind = 0) {
@@ -1313,6 +1350,10 @@ int launch_alt_mfma_r(const float* f1, const float* coords, float* out, const Al
       hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, 2, true, 1, DMA>), grid,
                          dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x,
                          reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL, 0);
+    else if constexpr (INBF)
+      hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minwbf(R), true, PF, 0, 0, false, OUTX, true, true>),
+                         grid, dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x,
+                         reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL, okind);
     else if constexpr (IN16)
       hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw16(R), true, PF, 0, 0, false, OUTX, true>),
                          grid, dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x,
@@ -1323,7 +1364,10 @@ int launch_alt_mfma_r(const float* f1, const float* coords, float* out, const Al
                          reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL, okind);
     return dxr::launch_status();
   }
-  if constexpr (IN16)
+  if constexpr (INBF)
+    hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minwbf(R), false, 1, 0, 0, false, OUTX, true, true>), grid,
+                       dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x, nullptr, 0, 0, okind);
+  else if constexpr (IN16)
     hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw16(R), false, 1, 0, 0, false, OUTX, true>), grid,
                        dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x, nullptr, 0, 0, okind);
   else
@@ -1347,7 +1391,8 @@ int launch_alt_r(const float* f1, const float* coords, float* out, const AltGeom
 // every flag combination; the VALU forms decline (DXR_EUNSUPPORTED, nothing
 // launched): a caller runs the unflagged call and converts.
 // IN16: float16 operands (alt_corr_in16.hip); the MFMA forms only, as the flags.
-template <bool OUTX = false, bool IN16 = false>
+// INBF (with IN16): bfloat16 operands (alt_corr_inbf16.hip).
+template <bool OUTX = false, bool IN16 = false, bool INBF = false>
 int launch_alt(const float* f1, const float* coords, float* out, const AltGeom& g, int levels,
                int Z, int radius, bool vec, hipStream_t stream, int W1 = 0,
                void* ord = nullptr, int okind = 0) {
@@ -1357,8 +1402,8 @@ int launch_alt(const float* f1, const float* coords, float* out, const AltGeom& 
   if (vec && W1 > 0 && g.C % 16 == 0 && g.C <= 256) {
 #define DXR_ALT_MFMA(RR)                                                                       \
   case RR:                                                                                     \
-    return launch_alt_mfma_r<RR, 1, 0, 4, 0, OUTX, IN16>(f1, coords, out, g, levels, Z, W1,    \
-                                                         stream, ord, -1, okind);
+    return launch_alt_mfma_r<RR, 1, 0, 4, 0, OUTX, IN16, INBF>(f1, coords, out, g, levels, Z,  \
+                                                               W1, stream, ord, -1, okind);
     switch (radius) {
       DXR_ALT_MFMA(0)
       DXR_ALT_MFMA(1)
@@ -1393,7 +1438,7 @@ float pow2_recip(float d) {
   return (m == 0.5f && e > -125 && e < 126) ? 1.f / d : 0.f;
 }
 
-#ifndef DXR_ALT_LOOKUP_TU   // alt_corr_out.hip / alt_corr_in16.hip take the lookup's flagged forms only
+#ifndef DXR_ALT_LOOKUP_TU   // alt_corr_out.hip / alt_corr_in16.hip / alt_corr_inbf16.hip take the lookup's flagged forms only
 // ---------------------------------------------------------------------------
 // alt_cuda_corr.backward, reference-FFI form (correlation_kernel.cu:122-256,
 // launched by :288-320).  For query q of pair b and coordinate set n, cell
@@ -1725,7 +1770,8 @@ namespace {
 // output (the rest come from dxr_alt_volume_lookup).
 // OUTX / okind: a flagged request (launch_alt); `out` then holds what okind says.
 // IN16: DXR_ALT_IN_F16 — fmap1 and fmap2_levels[0] point at float16.
-template <bool OUTX = false, bool IN16 = false>
+// INBF (with IN16): DXR_ALT_IN_BF16 — they point at bfloat16.
+template <bool OUTX = false, bool IN16 = false, bool INBF = false>
 int alt_lookup(const float* fmap1, const float* const* fmap2_levels, const float* coords, float* out,
                int64_t B, int64_t H, int64_t W, int64_t C, int num_levels, int radius,
                float divisor, void* workspace, int64_t workspace_bytes, hipStream_t stream,
@@ -1762,11 +1808,32 @@ int alt_lookup(const float* fmap1, const float* const* fmap2_levels, const float
   if (workspace != nullptr && aligned16(workspace) &&
       workspace_bytes >= (long long)B * nl * alt_order_bytes(H, W))
     ord = workspace;
-  return launch_alt<OUTX, IN16>(fmap1, coords, out, g, nl, (int)B, radius, vec, stream, (int)W, ord,
-                                okind);
+  return launch_alt<OUTX, IN16, INBF>(fmap1, coords, out, g, nl, (int)B, radius, vec, stream, (int)W,
+                                      ord, okind);
 }
 
-#if defined(DXR_ALT_IN16_TU)
+#if defined(DXR_ALT_INBF16_TU)
+}  // namespace
+
+// alt_corr_inbf16.hip: this file's lookup on bfloat16 fmaps (DXR_ALT_IN_BF16),
+// with and without output flags, and nothing else of it.
+int dxr::alt_lookup_inbf16(const void* fmap1, const void* const* fmap2_levels, const float* coords,
+                           void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W,
+                           int64_t C, int num_levels, int radius, float divisor, void* workspace,
+                           int64_t workspace_bytes, hipStream_t stream, int n_levels) {
+  const int okind = (out_flag == DXR_OUT_F16 ? 1 : 0) | (out_flag == DXR_OUT_BF16 ? 2 : 0) |
+                    (nhwc ? 4 : 0);
+  const float* f1 = static_cast<const float*>(fmap1);
+  const float* const* f2 = reinterpret_cast<const float* const*>(fmap2_levels);
+  if (okind == 0)
+    return alt_lookup<false, true, true>(f1, f2, coords, static_cast<float*>(out), B, H, W, C,
+                                         num_levels, radius, divisor, workspace, workspace_bytes,
+                                         stream, n_levels, 0);
+  return alt_lookup<true, true, true>(f1, f2, coords, static_cast<float*>(out), B, H, W, C,
+                                      num_levels, radius, divisor, workspace, workspace_bytes, stream,
+                                      n_levels, okind);
+}
+#elif defined(DXR_ALT_IN16_TU)
 }  // namespace
 
 // alt_corr_in16.hip: this file's lookup on float16 fmaps (DXR_ALT_IN_F16), with
@@ -2283,10 +2350,15 @@ int alt_lookup_entry(const float* fmap1, const float* const* fmap2_levels, const
   if (radius >= 0) {
     int out_flag;
     bool nhwc;
-    const bool in16 = (radius & DXR_ALT_IN_F16) != 0;
-    radius &= ~DXR_ALT_IN_F16;
+    const bool in16 = (radius & DXR_ALT_IN_F16) != 0, inbf = (radius & DXR_ALT_IN_BF16) != 0;
+    if (in16 && inbf) return DXR_EINVAL;   // one input dtype
+    radius &= ~(DXR_ALT_IN_F16 | DXR_ALT_IN_BF16);
     if (!dxr::split_out_flags(&radius, &out_flag, &nhwc)) return DXR_EINVAL;
     if (out_flag != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return DXR_EINVAL;
+    if (inbf)   // bfloat16 fmap1 and level 0, with or without output flags
+      return dxr::alt_lookup_inbf16(fmap1, reinterpret_cast<const void* const*>(fmap2_levels),
+                                    coords, out, out_flag, nhwc, B, H, W, C, num_levels, radius,
+                                    divisor, workspace, workspace_bytes, stream, n_levels);
     if (in16)   // float16 fmap1 and level 0, with or without output flags
       return dxr::alt_lookup_in16(fmap1, reinterpret_cast<const void* const*>(fmap2_levels), coords,
                                   out, out_flag, nhwc, B, H, W, C, num_levels, radius, divisor,
@@ -2330,12 +2402,13 @@ extern "C" int dxr_alt_corr_lookup_levels_ws(const float* fmap1, const float* co
                                              int radius, float divisor, void* workspace,
                                              int64_t workspace_bytes, hipStream_t stream) {
   {   // invalid output flags answer first, as in the other lookups
-    int r = radius & ~DXR_ALT_IN_F16, f;
+    int r = radius & ~(DXR_ALT_IN_F16 | DXR_ALT_IN_BF16), f;
     bool n;
+    if (radius >= 0 && (radius & DXR_ALT_IN_F16) && (radius & DXR_ALT_IN_BF16)) return DXR_EINVAL;
     if (radius >= 0 && !dxr::split_out_flags(&r, &f, &n)) return DXR_EINVAL;
   }
   if (n_levels < 1) return DXR_EINVAL;
   return alt_lookup_entry(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
                           workspace, workspace_bytes, stream, n_levels);
 }
-#endif  // DXR_ALT_IN16_TU / DXR_ALT_OUT_TU
+#endif  // DXR_ALT_INBF16_TU / DXR_ALT_IN16_TU / DXR_ALT_OUT_TU

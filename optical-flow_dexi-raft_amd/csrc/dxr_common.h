@@ -74,6 +74,13 @@ int alt_lookup_in16(const void* fmap1, const void* const* fmap2_levels, const fl
                     void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W, int64_t C,
                     int num_levels, int radius, float divisor, void* workspace,
                     int64_t workspace_bytes, hipStream_t stream, int n_levels);
+// The same with DXR_ALT_IN_BF16: fmap1 and fmap2_levels[0] point at bfloat16.
+// Defined in alt_corr_inbf16.hip, the only translation unit that instantiates
+// the bfloat16-operand forms.
+int alt_lookup_inbf16(const void* fmap1, const void* const* fmap2_levels, const float* coords,
+                      void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W, int64_t C,
+                      int num_levels, int radius, float divisor, void* workspace,
+                      int64_t workspace_bytes, hipStream_t stream, int n_levels);
 // dxr_alt_corr_backward with DXR_ALT_BWD_ACCUMULATE on `radius` (passed whole; B,
 // the map sizes and C already checked positive, radius >= 0): validation and
 // the MFMA kernel that adds into both gradients.  Defined in alt_corr_bwd.hip.
