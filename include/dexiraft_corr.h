@@ -168,6 +168,17 @@ enum dxr_dtype {
  */
 #define DXR_ALT_IN_BF16 0x20000
 
+/*
+ * Cell type flag of the alternate block's coarse volumes: or-ed onto the
+ * `first_level` argument of dxr_alt_coarse_volumes / dxr_alt_coarse_volumes_ws
+ * (the low byte is the level), `volumes` holds IEEE float16 cells, stored by the
+ * volume GEMM itself; or-ed onto the `radius` of dxr_alt_volume_lookup, alone or
+ * with the output flags, the lookup reads such cells.  Semantics, served shapes
+ * and validation: "Float16 volumes" at dxr_alt_volume_numel.  On any other entry
+ * point the bit is an unknown flag.
+ */
+#define DXR_ALT_VOL_F16 0x40000
+
 enum dxr_layout {
   DXR_NCHW = 0,         /* fmaps [B, D, H, W] (core/raft.py:139-142)              */
   DXR_NHWC = 1          /* fmaps [B, H, W, D] (channels-last encoders, §8(f) row 4) */
@@ -756,6 +767,35 @@ int dxr_alt_corr_lookup_levels_ws(const float* fmap1, const float* const* fmap2_
  *                           then stages by LDS-DMA; a null or short workspace
  *                           falls back to dxr_alt_coarse_volumes.  0 bytes when
  *                           no level takes the GEMM; -1: bad geometry.
+ *
+ * Float16 volumes.  DXR_ALT_VOL_F16 halves the volumes' memory (about 333 MB of
+ * float32 per 1080p pair, levels 2-3).  No new tolerance is involved:
+ *   dxr_alt_coarse_volumes / dxr_alt_coarse_volumes_ws with the flag or-ed onto
+ *       `first_level` (the low byte is the level): `volumes` points at
+ *       dxr_alt_volume_numel(...) float16 elements (the count is in elements and
+ *       does not change; passed through the float* parameter) and must be 16-byte
+ *       aligned, else DXR_EINVAL.  Every stored cell is the unflagged call's
+ *       float32 cell for the same operands rounded once to float16 in the GEMM's
+ *       own stores: to nearest even, beyond 65504 to +-inf, subnormals kept, still
+ *       the raw dot product.  The layout is counted in elements, so the buffer is
+ *       the float32 buffer's .half() element for element over every written page.
+ *       A 32 x 32 tile goes to the bf16-split fallback on its float32 sums, as
+ *       unflagged: a finite sum that rounds to +-inf is stored as +-inf.
+ *   dxr_alt_volume_lookup with the flag or-ed onto `radius`, alone or with any
+ *       valid combination of DXR_OUT_F16 / DXR_OUT_BF16 / DXR_OUT_NHWC: `volumes`
+ *       holds float16 cells, which are widened on load (exact) before the float32
+ *       arithmetic.  The output is that of the unflagged call with the same output
+ *       flags on the widened float32 copy of the buffer, bit for bit, for radius
+ *       0..8 and NaN / inf / far coordinates.  The flag beside
+ *       DXR_ALT_IN_F16 / DXR_ALT_IN_BF16 or any other unknown bit is DXR_EINVAL.
+ * Served natively: C % 32 == 0 and every requested level a tiled level (num_levels
+ * <= 4: the volume GEMM's levels).  Any other valid request — C % 32 != 0, whose
+ * levels take the FULL box form, or a row-major level 4 and beyond — is
+ * DXR_EUNSUPPORTED, answered on the host before any launch; the caller builds the
+ * float32 volumes and rounds them, which is the same buffer by definition.
+ * dxr_alt_volume_numel and dxr_alt_coarse_volumes_ws_bytes do not take the bit
+ * (-1), every other entry point rejects it as an unknown bit (DXR_EINVAL;
+ * dxr_alt_corr_forward / _backward: DXR_EUNSUPPORTED, as for the other high bits).
  */
 int64_t dxr_alt_volume_numel(int64_t B, int64_t H, int64_t W, int num_levels, int first_level);
 int dxr_alt_coarse_volumes(const float* fmap1, const float* const* fmap2_levels,

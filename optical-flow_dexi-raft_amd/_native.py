@@ -35,6 +35,9 @@ DXR_ALT_BWD_ACCUMULATE = 0x2000
 DXR_ALT_IN_F16 = 0x8000
 # the same for bfloat16 fmaps (one input flag at a time)
 DXR_ALT_IN_BF16 = 0x20000
+# float16 coarse volumes: or-ed onto the first_level of dxr_alt_coarse_volumes / _ws (the GEMM
+# stores float16 cells) and onto the radius of dxr_alt_volume_lookup (which reads them)
+DXR_ALT_VOL_F16 = 0x40000
 DXR_NCHW, DXR_NHWC = 0, 1
 DXR_BUILD_AUTO, DXR_BUILD_EXACT_F32 = 0, 1
 

@@ -55,6 +55,7 @@ def _sources(experiments: bool = False) -> list[Path]:
                                                 # the alternate lookups' flagged forms (xp_alt's and
                                                 # xp_lookup's entry points call them)
                                                 CSRC / "corr_lookup_alt_out.hip",
+                                                CSRC / "corr_lookup_alt_vol16.hip",
                                                 CSRC / "alt_corr_out.hip",
                                                 CSRC / "alt_corr_in16.hip",
                                                 CSRC / "alt_corr_inbf16.hip",
@@ -84,7 +85,8 @@ FILE_FLAGS = {"corr_build.hip": ["-fno-slp-vectorize"], "corr_lookup.hip": ["-fn
               "corr_lookup_out16.hip": ["-fno-slp-vectorize"],
               "corr_lookup_pyr16.hip": ["-fno-slp-vectorize"],
               "corr_lookup_nhwc.hip": ["-fno-slp-vectorize"],
-              "corr_lookup_alt_out.hip": ["-fno-slp-vectorize"]}
+              "corr_lookup_alt_out.hip": ["-fno-slp-vectorize"],
+              "corr_lookup_alt_vol16.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src: Path, extra: list[str], out_dir: Path = BUILD_DIR) -> Path:

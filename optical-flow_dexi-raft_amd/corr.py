@@ -446,6 +446,31 @@ def _layout_flag(memory_format) -> int:
                      f"torch.channels_last; got {memory_format!r}")
 
 
+def _pop_volume_dtype(extensions: dict):
+    """The keyword-only ``volume_dtype=None`` of the alternate blocks' constructors.
+    It is taken from ``**extensions`` so that the constructors' declared keyword
+    defaults stay the two output options the C-ABI tests of those options pin;
+    any other keyword is the ``TypeError`` a declared signature would raise."""
+    volume_dtype = extensions.pop("volume_dtype", None)
+    if extensions:
+        raise TypeError("__init__() got an unexpected keyword argument "
+                        f"{next(iter(extensions))!r}")
+    return volume_dtype
+
+
+def _f16_volumes(volume_dtype) -> bool:
+    """Whether ``AlternateCorrBlock(..., volume_dtype=...)`` asks for float16 coarse
+    volumes (``DXR_ALT_VOL_F16``): None / torch.float32 keep the float32 volumes,
+    torch.float16 halves them; anything else raises ``ValueError``."""
+    if volume_dtype is None:
+        return False
+    if not isinstance(volume_dtype, torch.dtype) or \
+            volume_dtype not in (torch.float32, torch.float16):
+        raise ValueError("volume_dtype must be None, torch.float32 or torch.float16; "
+                         f"got {volume_dtype!r}")
+    return volume_dtype == torch.float16
+
+
 def _empty_out(shape, dtype, device, layout_flag: int) -> torch.Tensor:
     """The output tensor of a lookup: ``[B, C, H, W]``, channels-last strides
     when the kernel stores channels-last."""
@@ -917,6 +942,35 @@ class AlternateCorrBlock:
     every RAFT model) and the volume lookup do this natively; for other D the
     library declines the flags (``DXR_EUNSUPPORTED``) and ``_lookup`` runs the
     float32 NCHW call and converts with torch — the same tensor by definition.
+
+    Memory of the coarse volumes.  A block with volumes holds, beside its
+    O(H*W*D) operands, ``dxr_alt_volume_numel`` cells: about 333 MB of float32 per
+    1080p pair (levels 2-3, B = 1; about 1 GB at B = 3), up to the 1 GiB cap
+    ``COARSE_VOLUME_MAX_BYTES``, beyond which a level or all volumes are dropped
+    and those levels run on the fly.  ``volume_dtype`` (keyword-only; None /
+    torch.float32: as described so far, torch.float16; anything else raises
+    ``ValueError`` before the fmaps are looked at) selects float16 volumes, half
+    that memory.  No new tolerance: every cell is the float32 volume's cell
+    rounded once to float16 (to nearest even, beyond 65504 to +-inf, subnormals
+    kept; the volume GEMM stores them so itself, ``DXR_ALT_VOL_F16``), a lookup
+    widens cells on load (exact) and runs the float32 arithmetic, so every
+    output is that of a float32-volume block whose volumes are
+    ``.half().float()`` of themselves, bit for bit, under every ``out_dtype`` /
+    ``memory_format``; the on-the-fly levels ``[0, coarse_first_level)`` are
+    untouched.  Against the float32-volume block a coarse level's outputs differ
+    by at most ((2^-11 + 2^-21) Vmax + 2^-25) / sqrt(D), Vmax the level's largest
+    |cell|.  The cap counts the volumes' real bytes, so a float16 block may keep a
+    level or a batch the float32 block drops.  The GEMM serves D % 32 == 0 and at
+    most 4 levels; otherwise (``DXR_EUNSUPPORTED``) the block builds the float32
+    volumes and keeps their ``.half()`` — the same buffer by definition, with a
+    transient peak of 1.5 times the float32 volumes during construction.  It works
+    with float32, float16 and bfloat16 fmaps (the volumes come from the transient
+    float32 fmap1 as before).  A block without volumes (small maps) accepts and
+    ignores the argument; the read-only ``volume_dtype`` reports what the block
+    holds (None without volumes).
+    The volumes are computed in the constructor: the fmaps must not be modified
+    after construction (the volumes would go stale, and channels-last fmaps are
+    read in place by every lookup).
     """
 
     # Which levels are precomputed (round 6, bench.py --block alt, profiles/r06/experiments/
@@ -941,10 +995,12 @@ class AlternateCorrBlock:
     NATIVE_BF16 = True
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, out_dtype=None,
-                 memory_format=None):
+                 memory_format=None, **extensions):
+        volume_dtype = _pop_volume_dtype(extensions)
         self.num_levels = num_levels
         self.radius = radius
         self._out_torch, self._out_flags = _out_flag(out_dtype)
+        self._vol16 = _f16_volumes(volume_dtype)
         self._out_layout = _layout_flag(memory_format)
         self._out_flags |= self._out_layout
         self._out_native = True   # until the library declines the flags (a VALU form)
@@ -997,8 +1053,8 @@ class AlternateCorrBlock:
             self._make_volumes(B, D, H, W)
 
     # Introspection reports the reference's constructor (core/corr.py:64), as
-    # CorrBlock's does: ``out_dtype`` and ``memory_format`` are extensions on top
-    # of its four arguments (class docstring; tests/test_api_cpu.py).
+    # CorrBlock's does: ``out_dtype``, ``memory_format`` and ``volume_dtype`` are extensions
+    # on top of its four arguments (class docstring; tests/test_api_cpu.py).
     __init__.__signature__ = inspect.Signature([
         inspect.Parameter("self", inspect.Parameter.POSITIONAL_OR_KEYWORD),
         inspect.Parameter("fmap1", inspect.Parameter.POSITIONAL_OR_KEYWORD),
@@ -1013,12 +1069,14 @@ class AlternateCorrBlock:
                       if sizes[lvl][0] * sizes[lvl][1] <= self.COARSE_LEVEL_MAX_CELLS), None)
         while first is not None and first < self.num_levels:
             n = lib.dxr_alt_volume_numel(B, H, W, self.num_levels, first)
-            if 0 < n * 4 <= self.COARSE_VOLUME_MAX_BYTES:
+            if 0 < n * (2 if self._vol16 else 4) <= self.COARSE_VOLUME_MAX_BYTES:   # real bytes
                 break
             first += 1
         if first is None or first >= self.num_levels:
             return
-        vol = torch.empty((n,), dtype=torch.float32, device=self._device)
+        vol = torch.empty((n,), dtype=torch.float16 if self._vol16 else torch.float32,
+                          device=self._device)
+        vflag = nat.DXR_ALT_VOL_F16 if self._vol16 else 0
         # with COARSE_VOLUME_PLANES, the f16 pair planes of the operands (the volume GEMM's
         # LDS-DMA form), from torch's caching allocator: freed once the launches that read
         # them have run; 0 bytes: the register form
@@ -1030,11 +1088,29 @@ class AlternateCorrBlock:
         f1 = self._f1_nhwc.float()   # (a no-op on float32 operands)
         with _Launch(self._device):
             st = lib.dxr_alt_coarse_volumes_ws(f1.data_ptr(), self._f2_ptrs, B, H, W, D,
-                                               self.num_levels, first, vol.data_ptr(), nat.ptr(ws),
-                                               max(nbytes, 0), nat.stream_of(vol))
+                                               self.num_levels, first | vflag, vol.data_ptr(),
+                                               nat.ptr(ws), max(nbytes, 0), nat.stream_of(vol))
+            if vflag and st == nat.DXR_EUNSUPPORTED:
+                # D % 32 != 0 or more than 4 levels (the FULL form and row-major levels store
+                # float32): the float32 volumes, rounded once — the same buffer by definition.
+                # Transient peak: the float32 volumes beside their float16 copy, 1.5 times the
+                # float32 block's volume memory, until the float32 buffer is freed below.
+                vol32 = torch.empty((n,), dtype=torch.float32, device=self._device)
+                st = lib.dxr_alt_coarse_volumes_ws(f1.data_ptr(), self._f2_ptrs, B, H, W, D,
+                                                   self.num_levels, first, vol32.data_ptr(),
+                                                   nat.ptr(ws), max(nbytes, 0),
+                                                   nat.stream_of(vol))
+                if st == nat.DXR_OK:
+                    vol.copy_(vol32)
+                del vol32
         nat.check(st, "AlternateCorrBlock coarse volumes (dxr_alt_coarse_volumes_ws)")
         self.coarse_first_level = first
         self._volumes = vol
+
+    @property
+    def volume_dtype(self):
+        """dtype of the coarse volumes the block holds (None: no volumes)."""
+        return None if self._volumes is None else self._volumes.dtype
 
     @property
     def pyramid(self):
@@ -1137,10 +1213,12 @@ class AlternateCorrBlock:
                 if flags and st == nat.DXR_EUNSUPPORTED and self.radius <= 6:
                     return None
                 nat.check(st, "AlternateCorrBlock lookup (dxr_alt_corr_lookup_levels_ws)")
-            # (the volumes are float32 whatever the fmaps: no input flag there)
+            # (the volumes are float32 or float16 whatever the fmaps: no input flag there)
+            vflag = nat.DXR_ALT_VOL_F16 if self._volumes.dtype == torch.float16 else 0
             st = lib.dxr_alt_volume_lookup(self._volumes.data_ptr(), c.data_ptr(), out.data_ptr(),
-                                           B, H, W, self.num_levels, first, self.radius | flags,
-                                           _sqrt_dim(D), nat.stream_of(c))
+                                           B, H, W, self.num_levels, first,
+                                           self.radius | flags | vflag, _sqrt_dim(D),
+                                           nat.stream_of(c))
         nat.check(st, "AlternateCorrBlock lookup (dxr_alt_volume_lookup)")
         return out
 
@@ -1190,25 +1268,35 @@ class TrainableAlternateCorrBlock(AlternateCorrBlock):
     tolerance, except that that kernel returns NaN for a query with a NaN or
     infinite coordinate where the MFMA kernel drops it (exactly 0).  Fmaps and
     ``grad_out`` must be finite.  Coords that require grad raise
-    ``NotImplementedError``, as everywhere; bad ``out_dtype`` / ``memory_format``
-    raise ``ValueError`` before the native library is reached.
+    ``NotImplementedError``, as everywhere; bad ``out_dtype`` / ``memory_format`` /
+    ``volume_dtype`` raise ``ValueError`` before the native library is reached.
+    ``volume_dtype=torch.float16`` with fmaps that require grad raises
+    ``NotImplementedError`` before any launch, as ``CorrBlock``'s float16 pyramid
+    does: a rounded forward with an exact backward is not offered silently.
+    Without grad it behaves as the base class.
     """
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, out_dtype=None,
-                 memory_format=None):
+                 memory_format=None, **extensions):
+        volume_dtype = _pop_volume_dtype(extensions)
         _out_flag(out_dtype)
+        vol16 = _f16_volumes(volume_dtype)
         _layout_flag(memory_format)
         self._train = None
         self._bwd_native = True   # until the library declines the accumulate flag
         if isinstance(fmap1, torch.Tensor) and isinstance(fmap2, torch.Tensor) and \
                 _wants_grad(fmap1, fmap2):
             _fmap_geometry(fmap1, fmap2)
+            if vol16:
+                # a rounded forward with an exact backward is not offered silently
+                _require_no_grad(fmap1, fmap2,
+                                 what="float16 coarse volumes (volume_dtype=torch.float16)")
             if fmap1.dtype in (torch.bfloat16, torch.float16):
                 fmap1, fmap2 = fmap1.float(), fmap2.float()   # tracked: grads in the input dtype
             self._train = (fmap1, fmap2)
             fmap1, fmap2 = fmap1.detach(), fmap2.detach()
         super().__init__(fmap1, fmap2, num_levels, radius, out_dtype=out_dtype,
-                         memory_format=memory_format)
+                         memory_format=memory_format, volume_dtype=volume_dtype)
 
     __init__.__signature__ = AlternateCorrBlock.__init__.__signature__
 

@@ -1897,9 +1897,13 @@ constexpr int VG_STAGE = 8 * VG_BLK;          // [operand][plane][k step] blocks
 // XA (experiments only; 0 in the product): bit 0 stores only sums equal to
 // 12345.0 (none: an ablation of the stores), bit 1 writes the raw f32 bits as the
 // hi / lo planes (no split VALU; results meaningless), bit 2 skips the MFMAs.
-template <int T, bool DMA, int XA = 0>
+// CT: the stored cell type.  float: the sums as they are.  _Float16 (DXR_ALT_VOL_F16):
+// each float32 sum rounded once to nearest even in the store (v_cvt_f16_f32: overflow to
+// +-inf, subnormals kept), so the buffer is the float32 buffer's .half() element for
+// element; the non-finite test below looks at the float32 sums, before the rounding.
+template <int T, bool DMA, int XA = 0, typename CT = float>
 __global__ __launch_bounds__(256, 2) void alt_volume_gemm_kernel(
-    const float* __restrict__ f1, const float* __restrict__ f2, float* __restrict__ out,
+    const float* __restrict__ f1, const float* __restrict__ f2, CT* __restrict__ out,
     dxr::LevelLayout vl, int N, int C, int ngroups, const _Float16* __restrict__ p1,
     const _Float16* __restrict__ p2) {
   static_assert(T == 2 || T == 8 || T == 32 || T == 128, "tiled levels 0-3 only");
@@ -2130,7 +2134,23 @@ __global__ __launch_bounds__(256, 2) void alt_volume_gemm_kernel(
                                      acc[a][q][4 * g4 + 2], acc[a][q][4 * g4 + 3]);
         if constexpr ((XA & 1) != 0)
           if (v.x != 12345.f) continue;
-        if constexpr (T >= 4) {
+        if constexpr (std::is_same_v<CT, _Float16>) {
+          // float16 cells: the same runs as one 8-B store, or two 4-B stores (T = 2)
+          const uint32_t h01 = dxr::out16_bits<_Float16>(v.x) | (dxr::out16_bits<_Float16>(v.y) << 16);
+          const uint32_t h23 = dxr::out16_bits<_Float16>(v.z) | (dxr::out16_bits<_Float16>(v.w) << 16);
+          if constexpr (T >= 4) {
+            const int t = row / T;
+            if (grp * TPG + t < ntiles)
+              *reinterpret_cast<uint2*>(out + vl.off + ((page0 + t) * 128 + ql_) * T + row % T) =
+                  make_uint2(h01, h23);
+          } else {
+            const int t = row / 2;
+            if (grp * TPG + t < ntiles)
+              *reinterpret_cast<uint32_t*>(out + vl.off + ((page0 + t) * 128 + ql_) * 2) = h01;
+            if (grp * TPG + t + 1 < ntiles)
+              *reinterpret_cast<uint32_t*>(out + vl.off + ((page0 + t + 1) * 128 + ql_) * 2) = h23;
+          }
+        } else if constexpr (T >= 4) {
           const int t = row / T;
           if (grp * TPG + t < ntiles)
             *reinterpret_cast<float4*>(out + vl.off + ((page0 + t) * 128 + ql_) * T + row % T) = v;
@@ -2184,9 +2204,9 @@ int launch_split_planes(const float* in, _Float16* out, long long B, long long r
 }
 
 // one level's volume by alt_volume_gemm_kernel (tiled levels 0-3, C % 32 == 0);
-// with f16 pair planes of both operands (p1, p2) the LDS-DMA form
-template <int XA = 0>
-int launch_alt_volume_gemm(const float* f1, const float* f2, float* vol, const dxr::LevelLayout& vl,
+// with f16 pair planes of both operands (p1, p2) the LDS-DMA form; CT: the cell type
+template <int XA = 0, typename CT = float>
+int launch_alt_volume_gemm(const float* f1, const float* f2, CT* vol, const dxr::LevelLayout& vl,
                            int B, int N, int C, hipStream_t stream,
                            const _Float16* p1 = nullptr, const _Float16* p2 = nullptr) {
   const int T = vl.th * vl.tw;
@@ -2199,11 +2219,11 @@ int launch_alt_volume_gemm(const float* f1, const float* f2, float* vol, const d
   const bool dma = p1 != nullptr && p2 != nullptr;
 #define DXR_VG(TT)                                                                              \
   if (dma)                                                                                      \
-    hipLaunchKernelGGL((alt_volume_gemm_kernel<TT, true, XA>), grid, dim3(256), 0, stream, f1, \
-                       f2, vol, vl, N, C, ngroups, p1, p2);                                     \
+    hipLaunchKernelGGL((alt_volume_gemm_kernel<TT, true, XA, CT>), grid, dim3(256), 0, stream, \
+                       f1, f2, vol, vl, N, C, ngroups, p1, p2);                                 \
   else                                                                                          \
-    hipLaunchKernelGGL((alt_volume_gemm_kernel<TT, false, XA>), grid, dim3(256), 0, stream, f1,\
-                       f2, vol, vl, N, C, ngroups, p1, p2);
+    hipLaunchKernelGGL((alt_volume_gemm_kernel<TT, false, XA, CT>), grid, dim3(256), 0, stream, \
+                       f1, f2, vol, vl, N, C, ngroups, p1, p2);
   switch (T) {
     case 2: DXR_VG(2) break;
     case 8: DXR_VG(8) break;
@@ -2253,18 +2273,28 @@ long long alt_volume_planes_bytes(const dxr::Levels& L, int64_t B, int64_t H, in
 }
 
 // full_form: every level by the FULL box kernel (experiments: the round-6 first form);
-// ws (>= alt_volume_planes_bytes): the GEMM's LDS-DMA form on pre-split planes
+// ws (>= alt_volume_planes_bytes): the GEMM's LDS-DMA form on pre-split planes.
+// DXR_ALT_VOL_F16 on first_level (the low byte is the level): `volumes` holds float16
+// cells, stored by the volume GEMM itself, so every level must take that GEMM.
 int alt_coarse_volumes(const float* fmap1, const float* const* fmap2_levels, int64_t B, int64_t H,
                        int64_t W, int64_t C, int num_levels, int first_level, float* volumes,
                        hipStream_t stream, bool full_form, void* ws = nullptr,
                        int64_t ws_bytes = 0) {
+  // (any other bit above the low byte leaves first_level >= num_levels: DXR_EINVAL below)
+  const bool vol16 = first_level >= 0 && (first_level & ~0xff) == DXR_ALT_VOL_F16;
+  if (vol16) first_level &= 0xff;
   dxr::Levels L;
   if (!dxr::make_levels(B, H, W, num_levels, &L) || first_level < 0 || first_level >= num_levels)
     return DXR_EINVAL;
   if (C < 1 || B > 65535 || H * W > (1LL << 30)) return DXR_EINVAL;
   if (C % 16 != 0 || C > 256) return DXR_EUNSUPPORTED;
+  // float16 cells: the tiled GEMM's stores only (the FULL form and a row-major level store
+  // float32); the caller builds float32 volumes and rounds them: the same buffer
+  if (vol16 && (C % 32 != 0 || num_levels > dxr::TILED_LEVELS || full_form))
+    return DXR_EUNSUPPORTED;
   if (B == 0) return DXR_OK;
   if (!fmap1 || !fmap2_levels || !volumes || !aligned16(fmap1)) return DXR_EINVAL;
+  if (vol16 && !aligned16(volumes)) return DXR_EINVAL;
   AltGeom g;
   g.N = (int)(H * W);
   g.C = (int)C;
@@ -2297,8 +2327,12 @@ int alt_coarse_volumes(const float* fmap1, const float* const* fmap2_levels, int
                                            (int)C, stream);
         if (st != DXR_OK) return st;
       }
-      const int st = launch_alt_volume_gemm(fmap1, fmap2_levels[l], volumes, g.vlay, (int)B, g.N,
-                                            (int)C, stream, planes, p2);
+      const int st =
+          vol16 ? launch_alt_volume_gemm<0, _Float16>(fmap1, fmap2_levels[l],
+                                                      reinterpret_cast<_Float16*>(volumes), g.vlay,
+                                                      (int)B, g.N, (int)C, stream, planes, p2)
+                : launch_alt_volume_gemm(fmap1, fmap2_levels[l], volumes, g.vlay, (int)B, g.N,
+                                         (int)C, stream, planes, p2);
       if (st != DXR_OK) return st;
       continue;
     }

@@ -801,7 +801,9 @@ __global__ __launch_bounds__(NT_) void corr_lookup_qm_kernel(
   constexpr int RD = Q::RD, K = Q::K, QB = Q::QB, RSC = Q::RSC;
   // ALT with 16-bit and / or channels-last outputs: the float32 NCHW ALT kernel's
   // arithmetic, pinned instruction by instruction (out_store.h)
-  constexpr bool FLAGGED = ALT && (NHWC || !std::is_same_v<OT, float>);
+  // (float16 volume cells, PT = _Float16, take the pinned form under every output: the
+  // float32 lookup of the widened volume, NaN bits included)
+  constexpr bool FLAGGED = ALT && (NHWC || !std::is_same_v<OT, float> || !std::is_same_v<PT, float>);
   __shared__ __attribute__((aligned(16))) float cells[Q::NCELL * QB];
   __shared__ float2 xs[RD * Q::XP];   // {LDS column offset (int bits), fx}
   __shared__ float2 ys[RD * Q::XP];   // {LDS row offset (int bits), fy}
@@ -1837,9 +1839,11 @@ int corr_lookup_conv1x1_impl(const void* pyramid, int pyr_dtype, int64_t B, int6
 // levels [first, num_levels): launch_lookup_r's shapes and output policy.  OT /
 // NHWC: the 16-bit and channels-last stores of the product lookup (above), on this
 // call's channel slice of a num_levels-wide output; instantiated in
-// corr_lookup_alt_out.hip only (float, NCHW: here).
-template <int R, typename OT = float, bool NHWC = false>
-int launch_alt_volume_r(const float* vol, const float* coords, OT* out, const LookupGeom& g0,
+// corr_lookup_alt_out.hip only (float, NCHW: here).  PT: the volumes' cell type;
+// _Float16 (DXR_ALT_VOL_F16) is instantiated in corr_lookup_alt_vol16.hip only, for
+// every output form.
+template <int R, typename OT = float, bool NHWC = false, typename PT = float>
+int launch_alt_volume_r(const PT* vol, const float* coords, OT* out, const LookupGeom& g0,
                         int first, int B, hipStream_t stream) {
   using W = WideCfg<R>;
   LookupGeom g = g0;
@@ -1849,26 +1853,26 @@ int launch_alt_volume_r(const float* vol, const float* coords, OT* out, const Lo
     if constexpr (R <= 4) {
       if (wg32 <= 1024) {
         const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)nl, (unsigned)B);
-        hipLaunchKernelGGL((corr_lookup_qm_kernel<R, float, 256, 16, 1, false, 0, true, OT, true>), grid,
+        hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 256, 16, 1, false, 0, true, OT, true>), grid,
                            dim3(256), 0, stream, vol, coords, out, g);
         return dxr::launch_status();
       }
     }
     const dim3 grid((unsigned)((g.N + W::QB - 1) / W::QB), (unsigned)nl, (unsigned)B);
-    hipLaunchKernelGGL((corr_lookup_qm_kernel<R, float, 512, W::QB, 1, true, 0, true, OT, true>), grid,
+    hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 512, W::QB, 1, true, 0, true, OT, true>), grid,
                        dim3(512), 0, stream, vol, coords, out, g);
     return dxr::launch_status();
   } else {
   if (R <= 4 && wg32 <= 1024) {
     g.out_nt = g.N % 32 == 0 ? 1 : 0;
     const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)nl, (unsigned)B);
-    hipLaunchKernelGGL((corr_lookup_qm_kernel<R, float, 256, 16, 1, false, 0, true, OT>), grid, dim3(256), 0,
+    hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 256, 16, 1, false, 0, true, OT>), grid, dim3(256), 0,
                        stream, vol, coords, out, g);
     return dxr::launch_status();
   }
   g.out_nt = 1;
   const dim3 grid((unsigned)((g.N + W::QB - 1) / W::QB), (unsigned)nl, (unsigned)B);
-  hipLaunchKernelGGL((corr_lookup_qm_kernel<R, float, 512, W::QB, 1, true, 0, true, OT>), grid, dim3(512), 0,
+  hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 512, W::QB, 1, true, 0, true, OT>), grid, dim3(512), 0,
                      stream, vol, coords, out, g);
   return dxr::launch_status();
   }
@@ -1876,8 +1880,8 @@ int launch_alt_volume_r(const float* vol, const float* coords, OT* out, const Lo
 
 // dxr_alt_volume_lookup after its flags: the checks (before any launch), the
 // geometry and the launch.
-template <typename OT, bool NHWC = false>
-int alt_volume_lookup_impl(const float* volumes, const float* coords, OT* out, int64_t B, int64_t H,
+template <typename OT, bool NHWC = false, typename PT = float>
+int alt_volume_lookup_impl(const PT* volumes, const float* coords, OT* out, int64_t B, int64_t H,
                            int64_t W, int num_levels, int first_level, int radius, float divisor,
                            hipStream_t stream) {
   dxr::Levels L;
@@ -1905,15 +1909,15 @@ int alt_volume_lookup_impl(const float* volumes, const float* coords, OT* out, i
     g.lv[l].off -= L.off[first_level];
   }
   switch (radius) {
-    case 0: return launch_alt_volume_r<0, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 1: return launch_alt_volume_r<1, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 2: return launch_alt_volume_r<2, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 3: return launch_alt_volume_r<3, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 4: return launch_alt_volume_r<4, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 5: return launch_alt_volume_r<5, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 6: return launch_alt_volume_r<6, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 7: return launch_alt_volume_r<7, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 8: return launch_alt_volume_r<8, OT, NHWC>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 0: return launch_alt_volume_r<0, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 1: return launch_alt_volume_r<1, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 2: return launch_alt_volume_r<2, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 3: return launch_alt_volume_r<3, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 4: return launch_alt_volume_r<4, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 5: return launch_alt_volume_r<5, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 6: return launch_alt_volume_r<6, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 7: return launch_alt_volume_r<7, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
+    case 8: return launch_alt_volume_r<8, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
     default: return DXR_EUNSUPPORTED;
   }
 }
@@ -2002,6 +2006,26 @@ int dxr::alt_volume_lookup_out(const float* volumes, const float* coords, void* 
   return DXR_EINVAL;   // unflagged requests stay in corr_lookup.hip
 #undef DXR_ALT_VOL
 }
+#elif defined(DXR_LOOKUP_ALT_VOL16_TU)
+// corr_lookup_alt_vol16.hip: the alternate block's volume lookup on float16 volumes
+// (DXR_ALT_VOL_F16), every output form, and nothing else of this file.
+int dxr::alt_volume_lookup_vol16(const void* volumes, const float* coords, void* out, int out_flag,
+                                 bool nhwc, int64_t B, int64_t H, int64_t W, int num_levels,
+                                 int first_level, int radius, float divisor, hipStream_t stream) {
+#define DXR_ALT_VOL(OT, NHWC)                                                                      \
+  alt_volume_lookup_impl<OT, NHWC, _Float16>(static_cast<const _Float16*>(volumes), coords,        \
+                                             static_cast<OT*>(out), B, H, W, num_levels,           \
+                                             first_level, radius, divisor, stream)
+  if (nhwc) {
+    if (out_flag == DXR_OUT_F16) return DXR_ALT_VOL(_Float16, true);
+    if (out_flag == DXR_OUT_BF16) return DXR_ALT_VOL(__bf16, true);
+    return DXR_ALT_VOL(float, true);
+  }
+  if (out_flag == DXR_OUT_F16) return DXR_ALT_VOL(_Float16, false);
+  if (out_flag == DXR_OUT_BF16) return DXR_ALT_VOL(__bf16, false);
+  return DXR_ALT_VOL(float, false);
+#undef DXR_ALT_VOL
+}
 #elif defined(DXR_LOOKUP_OUT16_TU)
 // corr_lookup_out16.hip: this file's templates with the 16-bit output types, and
 // nothing else of it.
@@ -2035,10 +2059,16 @@ extern "C" int dxr_alt_volume_lookup(const float* volumes, const float* coords, 
                                      hipStream_t stream) {
   int out_flag;
   bool nhwc;
-  // the output flags on `radius` (DXR_OUT_F16 / DXR_OUT_BF16 / DXR_OUT_NHWC) first
+  // the flags on `radius` first: DXR_ALT_VOL_F16 (float16 volume cells), then the output
+  // flags (DXR_OUT_F16 / DXR_OUT_BF16 / DXR_OUT_NHWC)
   if (radius >= 0) {
+    const bool vol16 = (radius & DXR_ALT_VOL_F16) != 0;
+    radius &= ~DXR_ALT_VOL_F16;
     if (!dxr::split_out_flags(&radius, &out_flag, &nhwc)) return DXR_EINVAL;
     if (out_flag != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return DXR_EINVAL;
+    if (vol16)   // their own translation unit (corr_lookup_alt_vol16.hip)
+      return dxr::alt_volume_lookup_vol16(volumes, coords, out, out_flag, nhwc, B, H, W,
+                                          num_levels, first_level, radius, divisor, stream);
     if (out_flag != 0 || nhwc)   // their own translation unit (corr_lookup_alt_out.hip)
       return dxr::alt_volume_lookup_out(volumes, coords, out, out_flag, nhwc, B, H, W, num_levels,
                                         first_level, radius, divisor, stream);

@@ -91,6 +91,13 @@ int alt_backward_accumulate(const float* fmap1, const float* fmap2, const float*
 int alt_volume_lookup_out(const float* volumes, const float* coords, void* out, int out_flag,
                           bool nhwc, int64_t B, int64_t H, int64_t W, int num_levels,
                           int first_level, int radius, float divisor, hipStream_t stream);
+// dxr_alt_volume_lookup with DXR_ALT_VOL_F16 on `radius` (split off by the entry point;
+// `volumes` holds float16 cells; out_flag 0 / DXR_OUT_F16 / DXR_OUT_BF16, nhwc, any
+// combination or none).  Defined in corr_lookup_alt_vol16.hip, the only translation unit
+// that instantiates the volume lookup with the float16 cell type.
+int alt_volume_lookup_vol16(const void* volumes, const float* coords, void* out, int out_flag,
+                            bool nhwc, int64_t B, int64_t H, int64_t W, int num_levels,
+                            int first_level, int radius, float divisor, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
 // Pyramid layout ("paged" correlation volume).
