@@ -102,6 +102,15 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "dxr_alt_volume_lookup": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _f32, _vp]),
 }
 
+# Every symbol include/dexiraft_flow.h declares (prefix dxf_, its own ABI version; the same
+# shared object).
+FLOW_ABI_VERSION = 1
+FLOW_SIGNATURES: dict[str, tuple[object, list[object]]] = {
+    "dxf_abi_version": (_int, []),
+    "dxf_forward_interpolate_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "dxf_forward_interpolate": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+}
+
 _lock = threading.Lock()
 _lib: ctypes.CDLL | None = None
 
@@ -118,13 +127,17 @@ def load() -> ctypes.CDLL:
                     f"{LIB_PATH.name} not found next to {Path(__file__).name}; build it with "
                     "`python optical-flow_dexi-raft_amd/build.py` (hipcc, gfx950)")
             lib = ctypes.CDLL(str(LIB_PATH))
-            for name, (res, args) in SIGNATURES.items():
+            for name, (res, args) in (*SIGNATURES.items(), *FLOW_SIGNATURES.items()):
                 fn = getattr(lib, name)
                 fn.restype = res
                 fn.argtypes = args
             ver = lib.dxr_abi_version()
             if ver != ABI_VERSION:
                 raise ImportError(f"{LIB_PATH.name} ABI {ver} != expected {ABI_VERSION}; rebuild")
+            ver = lib.dxf_abi_version()
+            if ver != FLOW_ABI_VERSION:
+                raise ImportError(f"{LIB_PATH.name} flow ABI {ver} != expected {FLOW_ABI_VERSION}; "
+                                  "rebuild")
             _lib = lib
     return _lib
 

@@ -61,7 +61,10 @@ def _sources(experiments: bool = False) -> list[Path]:
                                                 CSRC / "alt_corr_inbf16.hip",
                                                 # the accumulating backward xp_alt's copy of
                                                 # dxr_alt_corr_backward dispatches to
-                                                CSRC / "alt_corr_bwd.hip"]
+                                                CSRC / "alt_corr_bwd.hip",
+                                                # forward_interpolate (dexiraft_flow.h): no
+                                                # experiment varies it, the target exports it too
+                                                CSRC / "flow_interp.hip"]
     return sorted(CSRC.glob("*.hip"))
 
 

@@ -8,6 +8,11 @@ The model is the caller's — the reference RAFT / Dexi+RAFT with this package's
 ``CorrBlock`` swapped in: the encoders, DexiNed and the
 update block are outside this repository's scope.
 
+``infer_sequence`` is the other protocol of evaluate.py (:22-50, the Sintel
+submission with ``warm_start=True``): the pairs of one sequence in order, each
+started from the previous pair's low-resolution flow pushed forward on the GPU
+(``utils.forward_interpolate``).
+
 Multi-GPU: one process per GPU (``torch.distributed.run``).  ``infer_pairs``
 takes the full list of pairs, runs the contiguous share ``shard.pair_range``
 gives this rank, and — when asked — all-gathers the unpadded flows to every
@@ -25,8 +30,9 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from .shard import gather_pairs, pair_range
+from .utils import forward_interpolate
 
-__all__ = ["InputPadder", "write_flo", "read_flo", "infer_pairs", "FLO_TAG"]
+__all__ = ["InputPadder", "write_flo", "read_flo", "infer_pairs", "infer_sequence", "FLO_TAG"]
 
 FLO_TAG = 202021.25   # 'PIEH' as a little-endian float32 (frame_utils.py:9,88)
 
@@ -119,3 +125,44 @@ def infer_pairs(model: Callable, image1: torch.Tensor, image2: torch.Tensor, ite
     h, w = image1.shape[-2:]
     local = torch.stack(flows) if flows else image1.new_empty((0, 2, h, w), dtype=torch.float32)
     return gather_pairs(local.contiguous(), total) if gather else local
+
+
+def infer_sequence(model: Callable, frames: torch.Tensor, iters: int = 12, mode: str = "sintel",
+                   warm_start: bool = True,
+                   flo_paths: Sequence[str | Path] | None = None) -> torch.Tensor:
+    """Full-resolution flows of one frame sequence, warm-started (evaluate.py:33-50).
+
+    ``frames``: [T, 3, H, W]; pair i is (frames[i], frames[i + 1]).  The loop is the
+    reference's: ``flow_prev = None`` at the sequence start, then
+    ``flow_low, flow_up = model(a, b, iters=iters, flow_init=flow_prev,
+    test_mode=True)`` (core/raft.py:165-166 adds ``flow_init`` to the start
+    coordinates) and, with ``warm_start``,
+    ``flow_prev = forward_interpolate(flow_low[0])[None]`` — this package's
+    ``forward_interpolate``, which keeps the low-resolution flow on the GPU where
+    the reference goes through the host and scipy.  Without ``warm_start`` every
+    pair gets ``flow_init=None``.  Returns [T - 1, 2, H, W] float32 flows;
+    ``flo_paths[i]``, when given, receives pair i's flow.
+
+    A sequence is sequential by nature (pair i + 1 starts from pair i's result), so
+    it is not sharded over the process group as ``infer_pairs`` is: ranks take
+    whole sequences, each calling this for its own.
+    """
+    if frames.dim() != 4 or frames.shape[0] < 2:
+        raise ValueError(f"frames must be [T, 3, H, W] with T >= 2, got {tuple(frames.shape)}")
+    pairs = int(frames.shape[0]) - 1
+    if flo_paths is not None and len(flo_paths) < pairs:
+        raise ValueError(f"{pairs} pairs but only {len(flo_paths)} flo_paths")
+    padder = InputPadder(frames.shape, mode=mode)
+    flows = []
+    flow_prev = None
+    with torch.no_grad():
+        for i in range(pairs):
+            a, b = padder.pad(frames[i:i + 1], frames[i + 1:i + 2])
+            flow_low, flow_up = model(a, b, iters=iters, flow_init=flow_prev, test_mode=True)
+            if warm_start:
+                flow_prev = forward_interpolate(flow_low[0])[None]
+            flow = padder.unpad(flow_up[0]).float()
+            if flo_paths is not None:
+                write_flo(flo_paths[i], flow)
+            flows.append(flow)
+    return torch.stack(flows).contiguous()
