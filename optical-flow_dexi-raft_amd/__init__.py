@@ -9,6 +9,7 @@ Public surface, mirroring the reference's interface for this path:
   * ``alt_cuda_corr.forward / backward``  — alt_cuda_corr/correlation.cpp:51-54
   * ``coords_grid``                        — core/utils/utils.py:74-77
   * ``forward_interpolate``                — core/utils/utils.py:26-54, on the GPU
+  * ``upsample_flow``                      — core/raft.py:87-98, fused, with its backward
   * ``driver.InputPadder / write_flo / infer_pairs`` — core/utils/utils.py:7-24,
     core/utils/frame_utils.py:70-99, evaluate.py's per-pair loop (sharded)
   * ``driver.infer_sequence``              — evaluate.py:33-50, the warm-started sequence
@@ -16,8 +17,8 @@ Public surface, mirroring the reference's interface for this path:
 from . import alt_cuda_corr, driver
 from ._native import LIB_PATH, load as load_native
 from .corr import AlternateCorrBlock, CorrBlock, TrainableAlternateCorrBlock
-from .utils import coords_grid, forward_interpolate
+from .utils import coords_grid, forward_interpolate, upsample_flow
 
-__all__ = ["CorrBlock", "AlternateCorrBlock", "TrainableAlternateCorrBlock", "alt_cuda_corr", "coords_grid", "forward_interpolate", "driver", "load_native",
+__all__ = ["CorrBlock", "AlternateCorrBlock", "TrainableAlternateCorrBlock", "alt_cuda_corr", "coords_grid", "forward_interpolate", "upsample_flow", "driver", "load_native",
            "LIB_PATH"]
 __version__ = "0.1.0"

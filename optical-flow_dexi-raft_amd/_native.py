@@ -111,6 +111,18 @@ FLOW_SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "dxf_forward_interpolate": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
 }
 
+# Every symbol include/dexiraft_upsample.h declares (prefix dxu_, its own ABI version; the same
+# shared object).
+UPSAMPLE_ABI_VERSION = 1
+DXU_MASK_F32, DXU_MASK_F16, DXU_MASK_BF16 = 0, 1, 2   # enum dxu_mask_dtype
+UPSAMPLE_SIGNATURES: dict[str, tuple[object, list[object]]] = {
+    "dxu_abi_version": (_int, []),
+    "dxu_convex_upsample": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "dxu_convex_upsample_backward_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "dxu_convex_upsample_backward": (_int, [_vp, _vp, _int, _vp, _i64, _i64, _i64, _vp, _vp, _vp,
+                                            _i64, _vp]),
+}
+
 _lock = threading.Lock()
 _lib: ctypes.CDLL | None = None
 
@@ -127,7 +139,8 @@ def load() -> ctypes.CDLL:
                     f"{LIB_PATH.name} not found next to {Path(__file__).name}; build it with "
                     "`python optical-flow_dexi-raft_amd/build.py` (hipcc, gfx950)")
             lib = ctypes.CDLL(str(LIB_PATH))
-            for name, (res, args) in (*SIGNATURES.items(), *FLOW_SIGNATURES.items()):
+            for name, (res, args) in (*SIGNATURES.items(), *FLOW_SIGNATURES.items(),
+                                            *UPSAMPLE_SIGNATURES.items()):
                 fn = getattr(lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -138,6 +151,10 @@ def load() -> ctypes.CDLL:
             if ver != FLOW_ABI_VERSION:
                 raise ImportError(f"{LIB_PATH.name} flow ABI {ver} != expected {FLOW_ABI_VERSION}; "
                                   "rebuild")
+            ver = lib.dxu_abi_version()
+            if ver != UPSAMPLE_ABI_VERSION:
+                raise ImportError(f"{LIB_PATH.name} upsample ABI {ver} != expected "
+                                  f"{UPSAMPLE_ABI_VERSION}; rebuild")
             _lib = lib
     return _lib
 

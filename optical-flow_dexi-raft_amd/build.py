@@ -64,7 +64,9 @@ def _sources(experiments: bool = False) -> list[Path]:
                                                 CSRC / "alt_corr_bwd.hip",
                                                 # forward_interpolate (dexiraft_flow.h): no
                                                 # experiment varies it, the target exports it too
-                                                CSRC / "flow_interp.hip"]
+                                                CSRC / "flow_interp.hip",
+                                                # convex upsampling (dexiraft_upsample.h): likewise
+                                                CSRC / "flow_upsample.hip"]
     return sorted(CSRC.glob("*.hip"))
 
 

@@ -1,11 +1,12 @@
-"""Helpers of the lookup path and the warm start (reference core/utils/utils.py:26-54, 74-77)."""
+"""Helpers of the lookup path, the warm start and the upsampling (reference
+core/utils/utils.py:26-54, 74-77; core/raft.py:87-98)."""
 from __future__ import annotations
 
 import torch
 
 from . import _native
 
-__all__ = ["coords_grid", "forward_interpolate"]
+__all__ = ["coords_grid", "forward_interpolate", "upsample_flow"]
 
 
 def coords_grid(batch: int, ht: int, wd: int, device=None) -> torch.Tensor:
@@ -82,3 +83,103 @@ def forward_interpolate(flow: torch.Tensor) -> torch.Tensor:
                                                   _native.ptr(ws), nbytes, _native.stream_of(x)),
                       "dxf_forward_interpolate")
     return out
+
+
+_MASK_DTYPES = {torch.float32: _native.DXU_MASK_F32, torch.float16: _native.DXU_MASK_F16,
+                torch.bfloat16: _native.DXU_MASK_BF16}
+
+
+class _ConvexUpsample(torch.autograd.Function):
+    """flow: [N, 2, H, W] float32, mask: [N, 576, H, W] of a supported dtype, both
+    contiguous and on one HIP device.  Saves its two inputs and nothing else."""
+
+    @staticmethod
+    def forward(ctx, flow, mask):
+        ctx.save_for_backward(flow, mask)
+        lib = _native.load()
+        N, _, H, W = flow.shape
+        with torch.cuda.device(flow.device):
+            out = torch.empty((N, 2, 8 * H, 8 * W), dtype=torch.float32, device=flow.device)
+            _native.check(lib.dxu_convex_upsample(_native.ptr(mask), _MASK_DTYPES[mask.dtype],
+                                                  _native.ptr(flow), N, H, W, _native.ptr(out),
+                                                  _native.stream_of(flow)),
+                          "dxu_convex_upsample")
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        flow, mask = ctx.saved_tensors
+        need_flow, need_mask = ctx.needs_input_grad
+        if not (need_flow or need_mask):
+            return None, None
+        lib = _native.load()
+        N, _, H, W = flow.shape
+        g = grad_out.float().contiguous()
+        with torch.cuda.device(flow.device):
+            grad_flow = torch.empty_like(flow) if need_flow else None
+            grad_mask = torch.empty_like(mask) if need_mask else None
+            ws, nbytes = None, 0
+            if need_flow:
+                nbytes = lib.dxu_convex_upsample_backward_workspace_bytes(N, H, W)
+                ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=flow.device)
+            _native.check(lib.dxu_convex_upsample_backward(
+                _native.ptr(g), _native.ptr(mask), _MASK_DTYPES[mask.dtype], _native.ptr(flow),
+                N, H, W, _native.ptr(grad_mask), _native.ptr(grad_flow), _native.ptr(ws), nbytes,
+                _native.stream_of(flow)), "dxu_convex_upsample_backward")
+        return grad_flow, grad_mask
+
+
+def upsample_flow(flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """The reference's ``RAFT.upsample_flow`` (core/raft.py:87-98), fused, on the GPU.
+
+    ``flow``: ``[N, 2, H, W]``, ``mask``: ``[N, 576, H, W]`` (the update block's mask
+    head), on one HIP device.  Returns the ``[N, 2, 8H, 8W]`` float32 flow: fine
+    pixel ``(8h+i, 8w+j)`` is the convex combination of the 3x3 neighbourhood of
+    ``8 * flow`` around ``(h, w)`` (zeros outside the map) with the weights
+    ``softmax_k mask[n, 64k + 8i + j, h, w]``, ``k = 0..8``.  One HIP launch that
+    reads the mask once and writes the output once, where the reference runs
+    ``view -> softmax -> unfold -> multiply -> sum -> permute -> reshape``.
+
+    Differentiable in both arguments.  The backward recomputes the softmax from
+    the two inputs, which are all that is saved (the torch chain keeps the softmax
+    output of every iteration alive), honours ``needs_input_grad``, is
+    deterministic (no atomics) and takes two launches; its workspace and the
+    outputs come from torch's caching allocator, everything runs on torch's
+    current stream without a synchronisation, so forward and backward can sit
+    inside a captured graph.  Double backward is not supported and raises.
+
+    The mask may be float32, float16 or bfloat16 and is read in place; all
+    arithmetic is float32.  This is the one difference from the reference: with a
+    16-bit mask its softmax rounds the weights to 16 bits, here the result is the
+    float32 computation on ``mask.float()``.  ``grad_mask`` has the mask's dtype
+    (the float32 value rounded once).  A float16 / bfloat16 ``flow`` is widened
+    first.  Non-contiguous inputs, a channels-last mask included, are made
+    contiguous by a copy.
+
+    Host tensors raise ``RuntimeError`` (there is no CPU path); wrong ranks, a
+    channel count other than 2 / 576, mismatched ``N``/``H``/``W`` or tensors on
+    different devices ``ValueError``; other dtypes ``TypeError``.
+    """
+    for name, t in (("flow", flow), ("mask", mask)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    if flow.dim() != 4 or flow.shape[1] != 2:
+        raise ValueError(f"flow must be [N, 2, H, W], got {tuple(flow.shape)}")
+    if mask.dim() != 4 or mask.shape[1] != 576:
+        raise ValueError(f"mask must be [N, 576, H, W], got {tuple(mask.shape)}")
+    if (mask.shape[0], *mask.shape[2:]) != (flow.shape[0], *flow.shape[2:]):
+        raise ValueError(f"flow {tuple(flow.shape)} and mask {tuple(mask.shape)} differ in N, H or W")
+    if flow.device != mask.device:
+        raise ValueError(f"flow is on {flow.device}, mask on {mask.device}")
+    if mask.dtype not in _MASK_DTYPES:
+        raise TypeError(f"mask must be float32, float16 or bfloat16, got {mask.dtype}")
+    if flow.dtype not in _MASK_DTYPES:
+        raise TypeError(f"flow must be float32, float16 or bfloat16, got {flow.dtype}")
+    if not flow.is_cuda:
+        raise RuntimeError("upsample_flow: flow and mask must be on a HIP device (no CPU path)")
+    N, _, H, W = flow.shape
+    if N > 65535 or H < 1 or W < 1 or H * W > 2 ** 22:
+        raise ValueError(f"upsample_flow: unsupported geometry N={N}, H={H}, W={W} "
+                         "(N <= 65535, 1 <= H*W <= 2**22)")
+    return _ConvexUpsample.apply(flow.float().contiguous(), mask.contiguous())
