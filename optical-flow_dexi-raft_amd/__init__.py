@@ -10,6 +10,8 @@ Public surface, mirroring the reference's interface for this path:
   * ``coords_grid``                        — core/utils/utils.py:74-77
   * ``forward_interpolate``                — core/utils/utils.py:26-54, on the GPU
   * ``upsample_flow``                      — core/raft.py:87-98, fused, with its backward
+  * ``sequence_loss``                      — train.py:48-73, fused, with its backward
+  * ``flow_metrics``                       — the EPE reductions of evaluate.py, on the GPU
   * ``driver.InputPadder / write_flo / infer_pairs`` — core/utils/utils.py:7-24,
     core/utils/frame_utils.py:70-99, evaluate.py's per-pair loop (sharded)
   * ``driver.infer_sequence``              — evaluate.py:33-50, the warm-started sequence
@@ -17,8 +19,8 @@ Public surface, mirroring the reference's interface for this path:
 from . import alt_cuda_corr, driver
 from ._native import LIB_PATH, load as load_native
 from .corr import AlternateCorrBlock, CorrBlock, TrainableAlternateCorrBlock
-from .utils import coords_grid, forward_interpolate, upsample_flow
+from .utils import coords_grid, flow_metrics, forward_interpolate, sequence_loss, upsample_flow
 
-__all__ = ["CorrBlock", "AlternateCorrBlock", "TrainableAlternateCorrBlock", "alt_cuda_corr", "coords_grid", "forward_interpolate", "upsample_flow", "driver", "load_native",
-           "LIB_PATH"]
+__all__ = ["CorrBlock", "AlternateCorrBlock", "TrainableAlternateCorrBlock", "alt_cuda_corr", "coords_grid", "forward_interpolate", "upsample_flow", "sequence_loss", "flow_metrics", "driver",
+           "load_native", "LIB_PATH"]
 __version__ = "0.1.0"

@@ -123,6 +123,19 @@ UPSAMPLE_SIGNATURES: dict[str, tuple[object, list[object]]] = {
                                             _i64, _vp]),
 }
 
+# Every symbol include/dexiraft_loss.h declares (prefix dxl_, its own ABI version; the same
+# shared object).
+LOSS_ABI_VERSION = 1
+_f64 = ctypes.c_double
+LOSS_SIGNATURES: dict[str, tuple[object, list[object]]] = {
+    "dxl_abi_version": (_int, []),
+    "dxl_sequence_loss_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "dxl_sequence_loss": (_int, [ctypes.POINTER(_vp), _i64, _vp, _vp, _i64, _i64, _i64, _f64, _f32,
+                                 _vp, _vp, _vp, _vp, _i64, _vp]),
+    "dxl_sequence_loss_backward": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i64, _vp,
+                                          _vp, _i64, _i64, _i64, _f64, _f32, _vp]),
+}
+
 _lock = threading.Lock()
 _lib: ctypes.CDLL | None = None
 
@@ -140,7 +153,8 @@ def load() -> ctypes.CDLL:
                     "`python optical-flow_dexi-raft_amd/build.py` (hipcc, gfx950)")
             lib = ctypes.CDLL(str(LIB_PATH))
             for name, (res, args) in (*SIGNATURES.items(), *FLOW_SIGNATURES.items(),
-                                            *UPSAMPLE_SIGNATURES.items()):
+                                            *UPSAMPLE_SIGNATURES.items(),
+                                            *LOSS_SIGNATURES.items()):
                 fn = getattr(lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -155,6 +169,10 @@ def load() -> ctypes.CDLL:
             if ver != UPSAMPLE_ABI_VERSION:
                 raise ImportError(f"{LIB_PATH.name} upsample ABI {ver} != expected "
                                   f"{UPSAMPLE_ABI_VERSION}; rebuild")
+            ver = lib.dxl_abi_version()
+            if ver != LOSS_ABI_VERSION:
+                raise ImportError(f"{LIB_PATH.name} loss ABI {ver} != expected {LOSS_ABI_VERSION}; "
+                                  "rebuild")
             _lib = lib
     return _lib
 

@@ -66,7 +66,9 @@ def _sources(experiments: bool = False) -> list[Path]:
                                                 # experiment varies it, the target exports it too
                                                 CSRC / "flow_interp.hip",
                                                 # convex upsampling (dexiraft_upsample.h): likewise
-                                                CSRC / "flow_upsample.hip"]
+                                                CSRC / "flow_upsample.hip",
+                                                # sequence loss (dexiraft_loss.h): likewise
+                                                CSRC / "flow_loss.hip"]
     return sorted(CSRC.glob("*.hip"))
 
 

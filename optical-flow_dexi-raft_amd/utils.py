@@ -1,12 +1,15 @@
-"""Helpers of the lookup path, the warm start and the upsampling (reference
-core/utils/utils.py:26-54, 74-77; core/raft.py:87-98)."""
+"""Helpers of the lookup path, the warm start, the upsampling and the training
+loss (reference core/utils/utils.py:26-54, 74-77; core/raft.py:87-98;
+train.py:48-73)."""
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
 from . import _native
 
-__all__ = ["coords_grid", "forward_interpolate", "upsample_flow"]
+__all__ = ["coords_grid", "forward_interpolate", "upsample_flow", "sequence_loss", "flow_metrics"]
 
 
 def coords_grid(batch: int, ht: int, wd: int, device=None) -> torch.Tensor:
@@ -183,3 +186,167 @@ def upsample_flow(flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"upsample_flow: unsupported geometry N={N}, H={H}, W={W} "
                          "(N <= 65535, 1 <= H*W <= 2**22)")
     return _ConvexUpsample.apply(flow.float().contiguous(), mask.contiguous())
+
+
+def _pointer_array(tensors):
+    """Host array of device pointers (null for None), as the dxl_ entry points take it."""
+    return (ctypes.c_void_p * len(tensors))(*[_native.ptr(t) for t in tensors])
+
+
+def _loss_forward(preds, flow_gt, valid, gamma, max_flow, want_loss):
+    """dxl_sequence_loss on contiguous float32 tensors of one HIP device: (loss,
+    terms, stats), the first two None unless ``want_loss``."""
+    lib = _native.load()
+    B, _, H, W = flow_gt.shape
+    P, dev = len(preds), flow_gt.device
+    with torch.cuda.device(dev):
+        loss = torch.empty((), dtype=torch.float32, device=dev) if want_loss else None
+        terms = torch.empty(P, dtype=torch.float32, device=dev) if want_loss else None
+        stats = torch.empty(6, dtype=torch.float64, device=dev)
+        nbytes = lib.dxl_sequence_loss_workspace_bytes(P, B, H, W)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        _native.check(lib.dxl_sequence_loss(
+            _pointer_array(preds), P, _native.ptr(flow_gt), _native.ptr(valid), B, H, W, gamma,
+            max_flow, _native.ptr(loss), _native.ptr(terms), _native.ptr(stats), _native.ptr(ws),
+            nbytes, _native.stream_of(flow_gt)), "dxl_sequence_loss")
+    return loss, terms, stats
+
+
+class _SequenceLoss(torch.autograd.Function):
+    """flow_gt: [B, 2, H, W], valid: [B, H, W] or None, preds: P tensors like flow_gt;
+    all float32, contiguous, on one HIP device.  Saves references to its inputs and
+    nothing else; returns (loss, terms, stats), differentiable in the predictions
+    through ``loss`` only."""
+
+    @staticmethod
+    def forward(ctx, flow_gt, valid, gamma, max_flow, *preds):
+        ctx.save_for_backward(flow_gt, valid, *preds)
+        ctx.gamma, ctx.max_flow = gamma, max_flow
+        loss, terms, stats = _loss_forward(preds, flow_gt, valid, gamma, max_flow, True)
+        ctx.mark_non_differentiable(terms, stats)
+        return loss, terms, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, _grad_terms, _grad_stats):
+        flow_gt, valid, *preds = ctx.saved_tensors
+        need = ctx.needs_input_grad[4:]
+        if not any(need):
+            return (None,) * (4 + len(preds))
+        lib = _native.load()
+        B, _, H, W = flow_gt.shape
+        with torch.cuda.device(flow_gt.device):
+            g = grad_loss.float().contiguous()
+            grads = [torch.empty_like(p) if n else None for p, n in zip(preds, need)]
+            _native.check(lib.dxl_sequence_loss_backward(
+                _native.ptr(g), _pointer_array(preds), _pointer_array(grads), len(preds),
+                _native.ptr(flow_gt), _native.ptr(valid), B, H, W, ctx.gamma, ctx.max_flow,
+                _native.stream_of(flow_gt)), "dxl_sequence_loss_backward")
+        return (None, None, None, None, *grads)
+
+
+def _check_loss_inputs(what, preds, flow_gt, valid):
+    for name, t in (*((f"flow_preds[{i}]", p) for i, p in enumerate(preds)), ("flow_gt", flow_gt),
+                    *((("valid", valid),) if valid is not None else ())):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    if not 1 <= len(preds) <= 32:
+        raise ValueError(f"{what}: 1 to 32 predictions, got {len(preds)}")
+    if flow_gt.dim() != 4 or flow_gt.shape[1] != 2:
+        raise ValueError(f"flow_gt must be [B, 2, H, W], got {tuple(flow_gt.shape)}")
+    B, _, H, W = flow_gt.shape
+    for i, p in enumerate(preds):
+        if p.shape != flow_gt.shape:
+            raise ValueError(f"flow_preds[{i}] is {tuple(p.shape)}, flow_gt {tuple(flow_gt.shape)}")
+    if valid is not None and tuple(valid.shape) != (B, H, W):
+        raise ValueError(f"valid must be [B, H, W] = {(B, H, W)}, got {tuple(valid.shape)}")
+    if B < 1 or H < 1 or W < 1 or B * H * W > 2 ** 31:
+        raise ValueError(f"{what}: unsupported geometry B={B}, H={H}, W={W} "
+                         "(B, H, W >= 1, B*H*W <= 2**31)")
+    for i, p in enumerate((flow_gt, *preds)):
+        if p.device != flow_gt.device or (valid is not None and valid.device != flow_gt.device):
+            raise ValueError(f"{what}: tensors on different devices")
+        if not p.is_floating_point():
+            raise TypeError(f"{what}: flows must be floating point, got {p.dtype}")
+    if not flow_gt.is_cuda:
+        raise RuntimeError(f"{what}: the tensors must be on a HIP device (no CPU path)")
+
+
+def sequence_loss(flow_preds, flow_gt, valid, gamma=0.8, max_flow=400.0, *, sync_metrics=True):
+    """The reference's ``sequence_loss`` (train.py:48-73), fused, on the GPU.
+
+    ``flow_preds``: 1 to 32 predictions ``[B, 2, H, W]``, ``flow_gt``: ``[B, 2, H, W]``,
+    ``valid``: ``[B, H, W]`` (or ``None``: all valid), on one HIP device.  Returns
+    ``(loss, metrics)`` as the reference does.  With ``M = 2*B*H*W``::
+
+        v      = (valid >= 0.5) & (sqrt(gx*gx + gy*gy) < max_flow)
+        term_i = (1/M) * sum v * |flow_preds[i] - flow_gt|
+        loss   = sum_i gamma**(P-1-i) * term_i
+
+    ``loss`` is a 0-dim float32 tensor, differentiable in every prediction that
+    requires grad (not in ``flow_gt`` or ``valid``): every gradient element is
+    ``+q_i``, ``-q_i`` or ``0`` with ``q_i = float32(gamma**(P-1-i) / M) * grad_loss``.
+    ``metrics`` is ``{'epe', '1px', '3px', '5px'}`` as Python floats, from the last
+    prediction over the pixels ``v`` selects, read with one device-to-host copy of
+    six numbers; with no pixel selected they are NaN, like the reference's empty
+    mean.  With ``sync_metrics=False`` nothing is copied or synchronised and
+    ``metrics`` is ``{'stats': float64[6], 'terms': float32[P]}`` on the device
+    (``stats`` as ``flow_metrics`` returns it), so the call can sit inside a
+    captured graph.
+
+    The forward is two HIP launches that read every prediction once, where the
+    reference runs six torch ops per prediction and nine reductions; the backward
+    is one launch that recomputes ``v`` and the signs from the inputs, which are
+    all that is saved (by reference).  No atomics: both are deterministic.  Sums
+    are float64 above 16 float32 additions per thread and a wave-wide tree.  As in
+    the reference, a non-finite prediction makes the loss NaN even at an invalid
+    pixel.  Double backward is not supported and raises.
+
+    Predictions of other floating dtypes are widened with ``.float()`` (autograd
+    carries the conversion), ``valid`` of any dtype is converted with ``.float()``,
+    non-contiguous inputs are copied.  Host tensors raise ``RuntimeError`` (there
+    is no CPU path); wrong ranks or shapes, an empty batch, more than 32
+    predictions or tensors on different devices ``ValueError``.
+    """
+    preds = list(flow_preds)
+    gamma, max_flow = float(gamma), float(max_flow)
+    if not gamma >= 0.0 or max_flow != max_flow:
+        raise ValueError(f"sequence_loss: gamma must be >= 0 and max_flow not NaN, got {gamma}, "
+                         f"{max_flow}")
+    _check_loss_inputs("sequence_loss", preds, flow_gt, valid)
+    loss, terms, stats = _SequenceLoss.apply(
+        flow_gt.detach().float().contiguous(),
+        None if valid is None else valid.detach().float().contiguous(), gamma, max_flow,
+        *(p.float().contiguous() for p in preds))
+    if not sync_metrics:
+        return loss, {"stats": stats, "terms": terms}
+    n, epe, px1, px3, px5, _ = stats.tolist()
+    nan = float("nan")
+    return loss, {"epe": epe / n if n else nan, "1px": px1 / n if n else nan,
+                  "3px": px3 / n if n else nan, "5px": px5 / n if n else nan}
+
+
+def flow_metrics(flow_pr, flow_gt, valid=None, max_flow=float("inf")):
+    """End-point-error statistics of one flow on the GPU (evaluate.py:93, 121-128,
+    154-169 without the copy of the flow to the host).
+
+    ``flow_pr``, ``flow_gt``: ``[B, 2, H, W]`` (or ``[2, H, W]``), ``valid``:
+    ``[B, H, W]`` (``[H, W]``) or ``None``.  Returns the float64 tensor
+    ``[count, sum epe, #(epe < 1), #(epe < 3), #(epe < 5), #(epe > 3 and epe/mag > 0.05)]``
+    on the device, over the pixels with ``valid >= 0.5`` and ``mag < max_flow``,
+    ``epe = |flow_pr - flow_gt|``, ``mag = |flow_gt|`` (float32 per pixel, exact
+    counts): mean EPE is ``s[1] / s[0]``, the pixel fractions ``s[2:5] / s[0]``,
+    KITTI's F1 ``100 * s[5] / s[0]``.  The forward of ``sequence_loss`` with one
+    prediction; no gradient, no synchronisation.
+    """
+    if isinstance(flow_pr, torch.Tensor) and flow_pr.dim() == 3:
+        flow_pr, flow_gt = flow_pr[None], flow_gt[None]
+        valid = None if valid is None else valid[None]
+    _check_loss_inputs("flow_metrics", [flow_pr], flow_gt, valid)
+    max_flow = float(max_flow)
+    if max_flow != max_flow:
+        raise ValueError("flow_metrics: max_flow must not be NaN")
+    with torch.no_grad():
+        return _loss_forward([flow_pr.float().contiguous()], flow_gt.float().contiguous(),
+                             None if valid is None else valid.float().contiguous(), 1.0,
+                             max_flow, False)[2]
