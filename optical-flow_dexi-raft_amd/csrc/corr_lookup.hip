@@ -54,12 +54,23 @@ constexpr int FAR_ORIGIN = -(1 << 29);  // window origin of far / non-finite que
 //   index = off + (b*qt + (q >> lqb)) * qstride + (q & (2^lqb - 1)) * S
 //         + ((y >> lth) * tx + (x >> ltw)) * pageS + (y & mh) * tw + (x & mw)
 // Row-major levels use lth = ltw = 30 (tile index 0 for in-range cells).
+// Divisors 1 ... DIV_SHORT_MAX_DIVISOR take the short division of grid_norm_short:
+// the range scripts/check_uniform_div.cpp covers exhaustively.  A level of size 1
+// (divisor 0: the reference divides by zero) and larger levels keep the full one.
+constexpr int DIV_SHORT_MAX_DIVISOR = 511;
+
 struct LevelAddr {
   int h, w;                 // true level size
   int lth, ltw, mh, mw;     // tile shifts / masks
   int tw, tx, lqb, qt;
   int lS, lpS;              // paged levels: log2 S, log2 pageS (shifts, not multiplies)
   long long off, qstride, S, pageS;
+  // phase 0's workgroup-uniform floats, prepared on the host so the kernels read them
+  // as scalars: the divisors w - 1, h - 1 of the coordinate round trip, their halves,
+  // and their correctly rounded reciprocals for the short division (grid_norm_short;
+  // both 0 where a divisor is outside its proven range: the level takes the full
+  // division)
+  float wm1, hm1, hwm1, hhm1, rw, rh;
 };
 
 struct LookupGeom {
@@ -90,6 +101,12 @@ LevelAddr level_addr(const dxr::LevelLayout& y) {
     a.lqb = 0; a.pageS = 0; a.qstride = a.S;
     a.lS = a.lpS = -1;
   }
+  a.wm1 = (float)(y.w - 1); a.hm1 = (float)(y.h - 1);
+  a.hwm1 = a.wm1 / 2.f; a.hhm1 = a.hm1 / 2.f;
+  const bool short_div = y.w - 1 >= 1 && y.w - 1 <= DIV_SHORT_MAX_DIVISOR &&
+                         y.h - 1 >= 1 && y.h - 1 <= DIV_SHORT_MAX_DIVISOR;
+  a.rw = short_div ? 1.f / a.wm1 : 0.f;   // IEEE host division: rn(1 / (w - 1))
+  a.rh = short_div ? 1.f / a.hm1 : 0.f;
   return a;
 }
 
@@ -104,6 +121,38 @@ __device__ __forceinline__ float load_cell(const PT* p) {
 __device__ __forceinline__ float sample_coord(float c, float sm1, float half_sm1) {
   const float gn = __fsub_rn(__fdiv_rn(__fmul_rn(2.f, c), sm1), 1.f);
   return __fmul_rn(__fadd_rn(gn, 1.f), half_sm1);
+}
+
+// The round trip's first half, g = x / sm1 - 1 (x = 2c), by a short division for a
+// divisor the whole workgroup shares: with r = rn(1 / sm1) from the host,
+//   q0 = rn(x r),  e = x - q0 sm1 (exact, one fma),  q = rn(q0 + e r).
+// scripts/check_uniform_div.cpp compares it with the IEEE quotient over all 2^32
+// x for every divisor 1 ... 511: g is the full division's bit for bit for every
+// finite x (q itself for 2^-100 <= |x| < 2^101; below that they differ only in a
+// subnormal quotient's last bits and the sign of a zero one, which q - 1 = -1
+// absorbs).  +-inf and NaN do not take this form (the fma makes inf - inf).
+__device__ __forceinline__ float grid_norm_short(float x, float sm1, float r) {
+  const float q0 = __fmul_rn(x, r);
+  const float e = __builtin_fmaf(-q0, sm1, x);
+  return __fsub_rn(__builtin_fmaf(e, r, q0), 1.f);
+}
+
+// Both axes' round trips of one sample, c = coords / 2^l + (j - r) given.  The
+// short division runs when the level has reciprocals (LevelAddr::rw) and every
+// lane of the wave holds finite coordinates — a wave-uniform choice, so the
+// common case executes one path; otherwise the wave takes sample_coord's full
+// division.  Same values either way (grid_norm_short).
+__device__ __forceinline__ void sample_coords(float cx, float cy, const LevelAddr& A, float& ux,
+                                              float& uy) {
+  const float x2 = __fmul_rn(2.f, cx), y2 = __fmul_rn(2.f, cy);
+  const bool odd = !(fabsf(x2) < INFINITY) || !(fabsf(y2) < INFINITY);   // inf or NaN
+  if (__builtin_expect(__float_as_int(A.rw) != 0 && __builtin_amdgcn_ballot_w64(odd) == 0, 1)) {
+    ux = __fmul_rn(__fadd_rn(grid_norm_short(x2, A.wm1, A.rw), 1.f), A.hwm1);
+    uy = __fmul_rn(__fadd_rn(grid_norm_short(y2, A.hm1, A.rh), 1.f), A.hhm1);
+  } else {
+    ux = sample_coord(cx, A.wm1, A.hwm1);
+    uy = sample_coord(cy, A.hm1, A.hhm1);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -142,6 +191,9 @@ struct WideCfg {
   static constexpr int SIT = (QB * G + NT - 1) / NT;     // phase-0 slots per thread
   static_assert((QB * G) % NT == 0 || QB * G < NT, "whole waves per phase-0 pass");
   static_assert(G <= 64, "a query's lane group must sit in one wave");
+  // group_min's DPP steps read lanes of the same 16-lane row: a row is wholly in or
+  // wholly out of a phase-0 pass, so no step reads an inactive lane
+  static_assert((QB * G) % 16 == 0 && NT % 64 == 0, "phase-0 passes cover whole DPP rows");
   static_assert(QB <= dxr::PAGE_Q && dxr::PAGE_Q % QB == 0, "a workgroup stays in one page");
 };
 
@@ -274,6 +326,9 @@ __device__ __forceinline__ void wide_phase0_load(const float* __restrict__ coord
                                                  int b, int q0, int tid, Phase0Coords<R, NT_, QB_>& c) {
   using C = WideCfg<R, NT_, QB_>;
   constexpr int QB = C::QB, G = C::G;
+  // the pair's two planes as scalar bases: one 64-bit product for both
+  const float* __restrict__ px = coords + (long long)b * 2 * g.N;
+  const float* __restrict__ py = px + g.N;
 #pragma unroll
   for (int it = 0; it < C::SIT; ++it) {
     const int slot = tid + it * C::NT;
@@ -281,8 +336,8 @@ __device__ __forceinline__ void wide_phase0_load(const float* __restrict__ coord
     if (slot >= QB * G) break;   // whole waves
     const int q = q0 + (slot >> C::LG);
     if (q < g.N) {
-      c.x[it] = coords[((long long)b * 2 + 0) * g.N + q];
-      c.y[it] = coords[((long long)b * 2 + 1) * g.N + q];
+      c.x[it] = px[q];
+      c.y[it] = py[q];
     }
   }
 }
@@ -292,10 +347,13 @@ __device__ __forceinline__ void wide_phase0_load(const float* __restrict__ coord
 // value as any other reduction order.
 template <int G>
 __device__ __forceinline__ int group_min(int v) {
-  if constexpr (G >= 2) v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));  // quad [1,0,3,2]
-  if constexpr (G >= 4) v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));  // quad [2,3,0,1]
-  if constexpr (G >= 8) v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false)); // row_half_mirror
-  if constexpr (G >= 16) v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false)); // row_mirror
+  // every lane of these permutations has a source lane, so the DPP's `old` value is
+  // never taken: left undefined (mov_dpp), the swizzle folds into the v_min itself
+  // instead of a copy and a v_mov_dpp in front of it
+  if constexpr (G >= 2) v = min(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true));  // quad [1,0,3,2]
+  if constexpr (G >= 4) v = min(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true));  // quad [2,3,0,1]
+  if constexpr (G >= 8) v = min(v, __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true)); // row_half_mirror
+  if constexpr (G >= 16) v = min(v, __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true)); // row_mirror
   if constexpr (G >= 32) v = min(v, __shfl_xor(v, 16));
   if constexpr (G >= 64) v = min(v, __shfl_xor(v, 32));
   return v;
@@ -319,9 +377,8 @@ __device__ __forceinline__ void wide_phase0_taps(const Phase0Coords<R, NT_, QB_>
     const int j = slot & (G - 1), qq = slot >> C::LG;
     const float cx = c.x[it], cy = c.y[it];
     const float inv = __builtin_ldexpf(1.f, -l);  // 2^-l, exact (no division)
-    const float wm1 = (float)(Wl - 1), hm1 = (float)(Hl - 1);
-    const float ux = sample_coord(__fadd_rn(cx * inv, (float)(j - R)), wm1, wm1 / 2.f);
-    const float uy = sample_coord(__fadd_rn(cy * inv, (float)(j - R)), hm1, hm1 / 2.f);
+    float ux, uy;
+    sample_coords(__fadd_rn(cx * inv, (float)(j - R)), __fadd_rn(cy * inv, (float)(j - R)), A, ux, uy);
     const float flx = floorf(ux), fly = floorf(uy);
     const bool act = j < RD;
     // a non-finite or huge sample makes its query far: FAR_ORIGIN propagates through the min
@@ -495,9 +552,8 @@ __device__ __forceinline__ void qm_phase0_taps(const Phase0Coords<R, NT_, QB_>& 
     const int j = slot & (G - 1), qq = slot >> C::LG;
     const float cx = c.x[it], cy = c.y[it];
     const float inv = __builtin_ldexpf(1.f, -l);
-    const float wm1 = (float)(Wl - 1), hm1 = (float)(Hl - 1);
-    const float ux = sample_coord(__fadd_rn(cx * inv, (float)(j - R)), wm1, wm1 / 2.f);
-    const float uy = sample_coord(__fadd_rn(cy * inv, (float)(j - R)), hm1, hm1 / 2.f);
+    float ux, uy;
+    sample_coords(__fadd_rn(cx * inv, (float)(j - R)), __fadd_rn(cy * inv, (float)(j - R)), A, ux, uy);
     const float flx = floorf(ux), fly = floorf(uy);
     const bool act = j < RD;
     int mx = 0x7fffffff, my = 0x7fffffff;
@@ -810,8 +866,18 @@ __global__ __launch_bounds__(NT_) void corr_lookup_qm_kernel(
   __shared__ int2 org[QB];
 
   const int tid = threadIdx.x;
-  const int l = blockIdx.y + g.l0, b = blockIdx.z;
+  const int b = blockIdx.z;
   const int q0 = blockIdx.x * QB;
+  // The coordinate loads go out first: their addresses need g.N alone, which
+  // arrives with the pointers.  The level's LevelAddr is a second, dependent
+  // scalar load (g.lv indexed by blockIdx.y + g.l0); read ahead of the coordinates
+  // it put two scalar round trips in front of them.
+  // (the empty asm keeps the coordinate pointer in the first batch of argument loads;
+  // sunk into the load's branch it was one more round trip)
+  asm volatile("" : : "s"(coords));
+  Phase0Coords<R, NT_, QB_> c;
+  wide_phase0_load<R, NT_, QB_>(coords, g, b, q0, tid, c);
+  const int l = blockIdx.y + g.l0;
   const LevelAddr A = g.lv[l];
   if constexpr (QB_ == 16) {   // one-round grids: finest level first (as the wide kernel)
     if (l == 0) __builtin_amdgcn_s_setprio(3);
@@ -820,8 +886,6 @@ __global__ __launch_bounds__(NT_) void corr_lookup_qm_kernel(
   }
 
   {
-    Phase0Coords<R, NT_, QB_> c;
-    wide_phase0_load<R, NT_, QB_>(coords, g, b, q0, tid, c);
     if constexpr (ALT) qm_phase0_alt<R, NT_, QB_, FLAGGED>(c, A, l, tid, xs, ys, org);
     else qm_phase0_taps<R, NT_, QB_>(c, A, l, tid, xs, ys, org);
   }

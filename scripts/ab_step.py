@@ -56,15 +56,19 @@ def main():
     import dexiraft_amd
     from dexiraft_amd import _native as nat
     lib = dexiraft_amd.load_native()
-    xp = ctypes.CDLL(str(nat.LIB_PATH.with_name("libdexiraft_corr_exp.so")))
     vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
-    xp.dxr_xp_build_tail.restype = i32
-    xp.dxr_xp_build_tail.argtypes = [vp, vp, i32, i32, i64, i64, i64, i64, vp, vp, i32, vp]
-    xp.dxr_xp_lookup.restype = i32
-    xp.dxr_xp_lookup.argtypes = [vp, i32, i64, i64, i64, i32, vp, vp, i32, vp, vp]
-    xp.dxr_xp_alt_lookup.restype = i32
-    xp.dxr_xp_alt_lookup.argtypes = [vp, ctypes.POINTER(vp), vp, vp, i64, i64, i64, i64, i32,
-                                     ctypes.c_float, vp, i32, vp]
+    # the experiments target is needed only by its own variants: product-only A/Bs
+    # (-1 against --prev-lib) run without it
+    needs_xp = any(v >= 0 or v == -6 for v in a.variants)
+    xp = ctypes.CDLL(str(nat.LIB_PATH.with_name("libdexiraft_corr_exp.so"))) if needs_xp else None
+    if xp is not None:
+        xp.dxr_xp_build_tail.restype = i32
+        xp.dxr_xp_build_tail.argtypes = [vp, vp, i32, i32, i64, i64, i64, i64, vp, vp, i32, vp]
+        xp.dxr_xp_lookup.restype = i32
+        xp.dxr_xp_lookup.argtypes = [vp, i32, i64, i64, i64, i32, vp, vp, i32, vp, vp]
+        xp.dxr_xp_alt_lookup.restype = i32
+        xp.dxr_xp_alt_lookup.argtypes = [vp, ctypes.POINTER(vp), vp, vp, i64, i64, i64, i64, i32,
+                                         ctypes.c_float, vp, i32, vp]
     prev = None
     if -3 in a.variants or -4 in a.variants or -5 in a.variants:
         prev = ctypes.CDLL(a.prev_lib)
