@@ -12,6 +12,7 @@ from __future__ import annotations
 import argparse
 import concurrent.futures as cf
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -46,30 +47,14 @@ def hipcc() -> str:
 
 
 def _sources(experiments: bool = False) -> list[Path]:
-    if experiments:   # each experiment includes its product source; capi.hip once
-        # (and the lookup's 16-bit instantiations, which xp_lookup's entry points call)
-        # and float16-pyramid and channels-last instantiations
-        return sorted(EXP_DIR.glob("*.hip")) + [CSRC / "capi.hip", CSRC / "corr_lookup_out16.hip",
-                                                CSRC / "corr_lookup_pyr16.hip",
-                                                CSRC / "corr_lookup_nhwc.hip",
-                                                # the alternate lookups' flagged forms (xp_alt's and
-                                                # xp_lookup's entry points call them)
-                                                CSRC / "corr_lookup_alt_out.hip",
-                                                CSRC / "corr_lookup_alt_vol16.hip",
-                                                CSRC / "alt_corr_out.hip",
-                                                CSRC / "alt_corr_in16.hip",
-                                                CSRC / "alt_corr_inbf16.hip",
-                                                # the accumulating backward xp_alt's copy of
-                                                # dxr_alt_corr_backward dispatches to
-                                                CSRC / "alt_corr_bwd.hip",
-                                                # forward_interpolate (dexiraft_flow.h): no
-                                                # experiment varies it, the target exports it too
-                                                CSRC / "flow_interp.hip",
-                                                # convex upsampling (dexiraft_upsample.h): likewise
-                                                CSRC / "flow_upsample.hip",
-                                                # sequence loss (dexiraft_loss.h): likewise
-                                                CSRC / "flow_loss.hip"]
-    return sorted(CSRC.glob("*.hip"))
+    product = sorted(CSRC.glob("*.hip"))
+    if not experiments:
+        return product
+    # Each experiment #includes the product source it varies and so stands in for
+    # it (entry points included); every other product source is linked as it is.
+    exps = sorted(EXP_DIR.glob("*.hip"))
+    varied = {m for e in exps for m in re.findall(r'#include "\.\./(\w+\.hip)"', e.read_text())}
+    return exps + [p for p in product if p.name not in varied]
 
 
 def _deps(experiments: bool = False) -> list[Path]:
@@ -87,18 +72,19 @@ def is_stale(lib: Path = LIB_PATH) -> bool:
 # Per-file flags.  corr_build.hip: no SLP vectorisation — packed f32 VALU
 # (v_pk_add_f32) beside MFMAs costs more issue cycles than the scalar pair it
 # replaces (MI355X_MICROARCH.md, cycle constants); measured r01: split build
-# 192 -> 182 us at Sintel, other kernels neutral.
-FILE_FLAGS = {"corr_build.hip": ["-fno-slp-vectorize"], "corr_lookup.hip": ["-fno-slp-vectorize"],
-              "corr_lookup_out16.hip": ["-fno-slp-vectorize"],
-              "corr_lookup_pyr16.hip": ["-fno-slp-vectorize"],
-              "corr_lookup_nhwc.hip": ["-fno-slp-vectorize"],
-              "corr_lookup_alt_out.hip": ["-fno-slp-vectorize"],
-              "corr_lookup_alt_vol16.hip": ["-fno-slp-vectorize"]}
+# 192 -> 182 us at Sintel, other kernels neutral.  The lookup (corr_lookup.hip
+# and every variant unit corr_lookup_*.hip) is built the same way; an
+# experiment (xp_*) takes the flags of the product source it varies.
+def file_flags(name: str) -> list[str]:
+    name = name.replace("xp_", "corr_")
+    if name == "corr_build.hip" or (name.startswith("corr_lookup") and name.endswith(".hip")):
+        return ["-fno-slp-vectorize"]
+    return []
 
 
 def _compile(src: Path, extra: list[str], out_dir: Path = BUILD_DIR) -> Path:
     obj = out_dir / (src.stem + ".o")
-    flags = FILE_FLAGS.get(src.name.replace("xp_", "corr_"), [])
+    flags = file_flags(src.name)
     cmd = [hipcc(), *CXXFLAGS, *flags, *extra, "-c", str(src), "-o", str(obj)]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:

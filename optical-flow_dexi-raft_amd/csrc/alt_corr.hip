@@ -29,12 +29,6 @@
 #include "dxr_common.h"
 #include "out_store.h"
 
-// alt_corr_out.hip, alt_corr_in16.hip and alt_corr_inbf16.hip include this file
-// for the lookup's flagged forms only.
-#if defined(DXR_ALT_OUT_TU) || defined(DXR_ALT_IN16_TU) || defined(DXR_ALT_INBF16_TU)
-#define DXR_ALT_LOOKUP_TU
-#endif
-
 namespace {
 
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -1399,34 +1393,16 @@ int launch_alt(const float* f1, const float* coords, float* out, const AltGeom& 
   // MFMA form: C a multiple of 16 (k16 steps) up to 256, 16-byte aligned rows;
   // the per-query VALU form otherwise.  With a workspace (`ord`) the queries are
   // ordered first (alt_bin_*_kernel).
-  if (vec && W1 > 0 && g.C % 16 == 0 && g.C <= 256) {
-#define DXR_ALT_MFMA(RR)                                                                       \
-  case RR:                                                                                     \
-    return launch_alt_mfma_r<RR, 1, 0, 4, 0, OUTX, IN16, INBF>(f1, coords, out, g, levels, Z,  \
-                                                               W1, stream, ord, -1, okind);
-    switch (radius) {
-      DXR_ALT_MFMA(0)
-      DXR_ALT_MFMA(1)
-      DXR_ALT_MFMA(2)
-      DXR_ALT_MFMA(3)
-      DXR_ALT_MFMA(4)
-      DXR_ALT_MFMA(5)
-      DXR_ALT_MFMA(6)
-      default: return DXR_EUNSUPPORTED;
-    }
-#undef DXR_ALT_MFMA
-  }
+  if (vec && W1 > 0 && g.C % 16 == 0 && g.C <= 256)
+    return dxr::dispatch_radius<6>(radius, [&](auto r) {
+      return launch_alt_mfma_r<decltype(r)::value, 1, 0, 4, 0, OUTX, IN16, INBF>(
+          f1, coords, out, g, levels, Z, W1, stream, ord, -1, okind);
+    });
   if constexpr (OUTX || IN16) return DXR_EUNSUPPORTED;
-  switch (radius) {
-    case 0: return launch_alt_r<0>(f1, coords, out, g, levels, Z, vec, stream);
-    case 1: return launch_alt_r<1>(f1, coords, out, g, levels, Z, vec, stream);
-    case 2: return launch_alt_r<2>(f1, coords, out, g, levels, Z, vec, stream);
-    case 3: return launch_alt_r<3>(f1, coords, out, g, levels, Z, vec, stream);
-    case 4: return launch_alt_r<4>(f1, coords, out, g, levels, Z, vec, stream);
-    case 5: return launch_alt_r<5>(f1, coords, out, g, levels, Z, vec, stream);
-    case 6: return launch_alt_r<6>(f1, coords, out, g, levels, Z, vec, stream);
-    default: return DXR_EUNSUPPORTED;
-  }
+  // (not discarded above: the flagged units instantiate the VALU forms too, as they always have)
+  return dxr::dispatch_radius<6>(radius, [&](auto r) {
+    return launch_alt_r<decltype(r)::value>(f1, coords, out, g, levels, Z, vec, stream);
+  });
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
@@ -1438,7 +1414,76 @@ float pow2_recip(float d) {
   return (m == 0.5f && e > -125 && e < 126) ? 1.f / d : 0.f;
 }
 
-#ifndef DXR_ALT_LOOKUP_TU   // alt_corr_out.hip / alt_corr_in16.hip / alt_corr_inbf16.hip take the lookup's flagged forms only
+// n_levels < 0: every level; else only levels [0, n_levels) of a num_levels-level
+// output (the rest come from dxr_alt_volume_lookup).
+// OUTX / okind: a flagged request (launch_alt); `out` then holds what okind says.
+// IN16: DXR_ALT_IN_F16 — fmap1 and fmap2_levels[0] point at float16.
+// INBF (with IN16): DXR_ALT_IN_BF16 — they point at bfloat16.
+template <bool OUTX = false, bool IN16 = false, bool INBF = false>
+int alt_lookup(const float* fmap1, const float* const* fmap2_levels, const float* coords, float* out,
+               int64_t B, int64_t H, int64_t W, int64_t C, int num_levels, int radius,
+               float divisor, void* workspace, int64_t workspace_bytes, hipStream_t stream,
+               int n_levels = -1, int okind = 0) {
+  dxr::Levels L;
+  if (!dxr::make_levels(B, H, W, num_levels, &L)) return DXR_EINVAL;
+  if (n_levels > num_levels || n_levels == 0) return DXR_EINVAL;
+  const int nl = n_levels < 0 ? num_levels : n_levels;
+  if (C < 1 || radius < 0 || !(divisor == divisor) || divisor == 0.f) return DXR_EINVAL;
+  if (radius > 6) return DXR_EUNSUPPORTED;
+  if (H * W > (1LL << 30) || B > 65535 || C > (1 << 20)) return DXR_EINVAL;
+  if (B == 0) return DXR_OK;
+  if (!fmap1 || !fmap2_levels || !coords || !out) return DXR_EINVAL;
+  const int rd = 2 * radius + 1;
+  AltGeom g;
+  g.N = (int)(H * W);
+  g.C = (int)C;
+  g.Nc = 1;
+  g.cout = num_levels * rd * rd;
+  g.divisor = divisor;
+  g.div_recip = pow2_recip(divisor);
+  g.f1_bstride = H * W * C;
+  g.coord_zstride = 2 * H * W;
+  g.coord_cstride = H * W;
+  g.coord_qstride = 1;
+  bool vec = (C % 4 == 0) && aligned16(fmap1);
+  for (int l = 0; l < nl; ++l) {
+    if (!fmap2_levels[l]) return DXR_EINVAL;
+    vec = vec && aligned16(fmap2_levels[l]);
+    g.lv[l] = AltLevel{fmap2_levels[l], L.h[l], L.w[l], 1.f / (float)(1 << l), l * rd * rd};
+  }
+  if constexpr (IN16) g.f16_levels = 1u;
+  void* ord = nullptr;
+  if (workspace != nullptr && aligned16(workspace) &&
+      workspace_bytes >= (long long)B * nl * alt_order_bytes(H, W))
+    ord = workspace;
+  return launch_alt<OUTX, IN16, INBF>(fmap1, coords, out, g, nl, (int)B, radius, vec, stream, (int)W,
+                                      ord, okind);
+}
+
+// A unit's whole shim: alt_lookup on its operand type for the request's output
+// form, FORMS being the forms the unit answers (out_store.h); OUTX and okind
+// follow from the form.
+template <unsigned FORMS, bool IN16 = false, bool INBF = false>
+int alt_lookup_forms(const dxr::AltLookupArgs& a) {
+  return dxr::dispatch_out_form<FORMS>(a.out_flag, a.nhwc, a.out, [&](auto* out, auto nhwc) {
+    constexpr int okind = dxr::out_kind<std::remove_pointer_t<decltype(out)>, decltype(nhwc)::value>();
+    return alt_lookup<okind != 0, IN16, INBF>(a.fmap1, a.fmap2_levels, a.coords,
+                                              static_cast<float*>(a.out), a.B, a.H, a.W, a.C,
+                                              a.num_levels, a.radius, a.divisor, a.workspace,
+                                              a.workspace_bytes, a.stream, a.n_levels, okind);
+  });
+}
+
+}  // namespace
+
+// Everything above is the lookup's templates.  The variant units (alt_corr_out.hip,
+// alt_corr_in16.hip, alt_corr_inbf16.hip) define DXR_TEMPLATES_ONLY and include this
+// file for them; what follows (the reference-FFI backward, the layout helpers, the
+// volume GEMM and every entry point) is this unit's alone.
+#ifndef DXR_TEMPLATES_ONLY
+
+namespace {
+
 // ---------------------------------------------------------------------------
 // alt_cuda_corr.backward, reference-FFI form (correlation_kernel.cu:122-256,
 // launched by :288-320).  For query q of pair b and coordinate set n, cell
@@ -1650,11 +1695,8 @@ __global__ __launch_bounds__(256) void avg_pool2x2_nhwc_kernel(const float* __re
   }
 }
 
-#endif  // DXR_ALT_LOOKUP_TU
-
 }  // namespace
 
-#ifndef DXR_ALT_LOOKUP_TU
 extern "C" int dxr_alt_corr_forward(const float* fmap1, const float* fmap2, const float* coords,
                                     float* corr, int64_t B, int64_t H1, int64_t W1, int64_t H2,
                                     int64_t W2, int64_t C, int64_t Nc, int radius,
@@ -1708,15 +1750,9 @@ extern "C" int dxr_alt_corr_backward(const float* fmap1, const float* fmap2, con
   }
   const AltBwd a{fmap1, fmap2, coords, corr_grad, fmap1_grad, fmap2_grad, (int)B,
                  (int)(H1 * W1), (int)H2, (int)W2, (int)C, (int)Nc};
-  switch (radius) {
-    case 0: return launch_alt_backward_r<0>(a, stream);
-    case 1: return launch_alt_backward_r<1>(a, stream);
-    case 2: return launch_alt_backward_r<2>(a, stream);
-    case 3: return launch_alt_backward_r<3>(a, stream);
-    case 4: return launch_alt_backward_r<4>(a, stream);
-    case 5: return launch_alt_backward_r<5>(a, stream);
-    default: return launch_alt_backward_r<6>(a, stream);
-  }
+  return dxr::dispatch_radius<6>(radius, [&](auto r) {
+    return launch_alt_backward_r<decltype(r)::value>(a, stream);
+  });
 }
 
 extern "C" int dxr_transpose(const void* in, void* out, int dtype, int64_t B, int64_t rows,
@@ -1763,112 +1799,7 @@ extern "C" int dxr_avg_pool2x2_nhwc(const float* in, float* out, int64_t B, int6
   return dxr::launch_status();
 }
 
-#endif  // DXR_ALT_LOOKUP_TU
-
 namespace {
-// n_levels < 0: every level; else only levels [0, n_levels) of a num_levels-level
-// output (the rest come from dxr_alt_volume_lookup).
-// OUTX / okind: a flagged request (launch_alt); `out` then holds what okind says.
-// IN16: DXR_ALT_IN_F16 — fmap1 and fmap2_levels[0] point at float16.
-// INBF (with IN16): DXR_ALT_IN_BF16 — they point at bfloat16.
-template <bool OUTX = false, bool IN16 = false, bool INBF = false>
-int alt_lookup(const float* fmap1, const float* const* fmap2_levels, const float* coords, float* out,
-               int64_t B, int64_t H, int64_t W, int64_t C, int num_levels, int radius,
-               float divisor, void* workspace, int64_t workspace_bytes, hipStream_t stream,
-               int n_levels = -1, int okind = 0) {
-  dxr::Levels L;
-  if (!dxr::make_levels(B, H, W, num_levels, &L)) return DXR_EINVAL;
-  if (n_levels > num_levels || n_levels == 0) return DXR_EINVAL;
-  const int nl = n_levels < 0 ? num_levels : n_levels;
-  if (C < 1 || radius < 0 || !(divisor == divisor) || divisor == 0.f) return DXR_EINVAL;
-  if (radius > 6) return DXR_EUNSUPPORTED;
-  if (H * W > (1LL << 30) || B > 65535 || C > (1 << 20)) return DXR_EINVAL;
-  if (B == 0) return DXR_OK;
-  if (!fmap1 || !fmap2_levels || !coords || !out) return DXR_EINVAL;
-  const int rd = 2 * radius + 1;
-  AltGeom g;
-  g.N = (int)(H * W);
-  g.C = (int)C;
-  g.Nc = 1;
-  g.cout = num_levels * rd * rd;
-  g.divisor = divisor;
-  g.div_recip = pow2_recip(divisor);
-  g.f1_bstride = H * W * C;
-  g.coord_zstride = 2 * H * W;
-  g.coord_cstride = H * W;
-  g.coord_qstride = 1;
-  bool vec = (C % 4 == 0) && aligned16(fmap1);
-  for (int l = 0; l < nl; ++l) {
-    if (!fmap2_levels[l]) return DXR_EINVAL;
-    vec = vec && aligned16(fmap2_levels[l]);
-    g.lv[l] = AltLevel{fmap2_levels[l], L.h[l], L.w[l], 1.f / (float)(1 << l), l * rd * rd};
-  }
-  if constexpr (IN16) g.f16_levels = 1u;
-  void* ord = nullptr;
-  if (workspace != nullptr && aligned16(workspace) &&
-      workspace_bytes >= (long long)B * nl * alt_order_bytes(H, W))
-    ord = workspace;
-  return launch_alt<OUTX, IN16, INBF>(fmap1, coords, out, g, nl, (int)B, radius, vec, stream, (int)W,
-                                      ord, okind);
-}
-
-#if defined(DXR_ALT_INBF16_TU)
-}  // namespace
-
-// alt_corr_inbf16.hip: this file's lookup on bfloat16 fmaps (DXR_ALT_IN_BF16),
-// with and without output flags, and nothing else of it.
-int dxr::alt_lookup_inbf16(const void* fmap1, const void* const* fmap2_levels, const float* coords,
-                           void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W,
-                           int64_t C, int num_levels, int radius, float divisor, void* workspace,
-                           int64_t workspace_bytes, hipStream_t stream, int n_levels) {
-  const int okind = (out_flag == DXR_OUT_F16 ? 1 : 0) | (out_flag == DXR_OUT_BF16 ? 2 : 0) |
-                    (nhwc ? 4 : 0);
-  const float* f1 = static_cast<const float*>(fmap1);
-  const float* const* f2 = reinterpret_cast<const float* const*>(fmap2_levels);
-  if (okind == 0)
-    return alt_lookup<false, true, true>(f1, f2, coords, static_cast<float*>(out), B, H, W, C,
-                                         num_levels, radius, divisor, workspace, workspace_bytes,
-                                         stream, n_levels, 0);
-  return alt_lookup<true, true, true>(f1, f2, coords, static_cast<float*>(out), B, H, W, C,
-                                      num_levels, radius, divisor, workspace, workspace_bytes, stream,
-                                      n_levels, okind);
-}
-#elif defined(DXR_ALT_IN16_TU)
-}  // namespace
-
-// alt_corr_in16.hip: this file's lookup on float16 fmaps (DXR_ALT_IN_F16), with
-// and without output flags, and nothing else of it.
-int dxr::alt_lookup_in16(const void* fmap1, const void* const* fmap2_levels, const float* coords,
-                         void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W,
-                         int64_t C, int num_levels, int radius, float divisor, void* workspace,
-                         int64_t workspace_bytes, hipStream_t stream, int n_levels) {
-  const int okind = (out_flag == DXR_OUT_F16 ? 1 : 0) | (out_flag == DXR_OUT_BF16 ? 2 : 0) |
-                    (nhwc ? 4 : 0);
-  const float* f1 = static_cast<const float*>(fmap1);
-  const float* const* f2 = reinterpret_cast<const float* const*>(fmap2_levels);
-  if (okind == 0)
-    return alt_lookup<false, true>(f1, f2, coords, static_cast<float*>(out), B, H, W, C, num_levels,
-                                   radius, divisor, workspace, workspace_bytes, stream, n_levels, 0);
-  return alt_lookup<true, true>(f1, f2, coords, static_cast<float*>(out), B, H, W, C, num_levels,
-                                radius, divisor, workspace, workspace_bytes, stream, n_levels, okind);
-}
-#elif defined(DXR_ALT_OUT_TU)
-}  // namespace
-
-// alt_corr_out.hip: this file's lookup with the flagged output forms, and nothing
-// else of it.
-int dxr::alt_lookup_out(const float* fmap1, const float* const* fmap2_levels, const float* coords,
-                        void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W,
-                        int64_t C, int num_levels, int radius, float divisor, void* workspace,
-                        int64_t workspace_bytes, hipStream_t stream, int n_levels) {
-  const int okind = (out_flag == DXR_OUT_F16 ? 1 : 0) | (out_flag == DXR_OUT_BF16 ? 2 : 0) |
-                    (nhwc ? 4 : 0);
-  if (okind == 0) return DXR_EINVAL;   // unflagged requests stay in alt_corr.hip
-  return alt_lookup<true>(fmap1, fmap2_levels, coords, static_cast<float*>(out), B, H, W, C,
-                          num_levels, radius, divisor, workspace, workspace_bytes, stream, n_levels,
-                          okind);
-}
-#else
 // ---------------------------------------------------------------------------
 // A coarse level's whole volume as one tiled GEMM (round 6): every (query, cell)
 // sum of the level, raw, into that level's pages of the volume buffer — the FULL
@@ -2381,29 +2312,20 @@ int alt_lookup_entry(const float* fmap1, const float* const* fmap2_levels, const
                      float* out, int64_t B, int64_t H, int64_t W, int64_t C, int num_levels,
                      int radius, float divisor, void* workspace, int64_t workspace_bytes,
                      hipStream_t stream, int n_levels) {
+  dxr::AltLookupArgs a{fmap1, fmap2_levels, coords, out, 0, false, B, H, W, C, num_levels, radius,
+                       divisor, workspace, workspace_bytes, stream, n_levels};
   if (radius >= 0) {
-    int out_flag;
-    bool nhwc;
     const bool in16 = (radius & DXR_ALT_IN_F16) != 0, inbf = (radius & DXR_ALT_IN_BF16) != 0;
     if (in16 && inbf) return DXR_EINVAL;   // one input dtype
-    radius &= ~(DXR_ALT_IN_F16 | DXR_ALT_IN_BF16);
-    if (!dxr::split_out_flags(&radius, &out_flag, &nhwc)) return DXR_EINVAL;
-    if (out_flag != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return DXR_EINVAL;
-    if (inbf)   // bfloat16 fmap1 and level 0, with or without output flags
-      return dxr::alt_lookup_inbf16(fmap1, reinterpret_cast<const void* const*>(fmap2_levels),
-                                    coords, out, out_flag, nhwc, B, H, W, C, num_levels, radius,
-                                    divisor, workspace, workspace_bytes, stream, n_levels);
-    if (in16)   // float16 fmap1 and level 0, with or without output flags
-      return dxr::alt_lookup_in16(fmap1, reinterpret_cast<const void* const*>(fmap2_levels), coords,
-                                  out, out_flag, nhwc, B, H, W, C, num_levels, radius, divisor,
-                                  workspace, workspace_bytes, stream, n_levels);
-    if (out_flag != 0 || nhwc)
-      return dxr::alt_lookup_out(fmap1, fmap2_levels, coords, out, out_flag, nhwc, B, H, W, C,
-                                 num_levels, radius, divisor, workspace, workspace_bytes, stream,
-                                 n_levels);
+    a.radius &= ~(DXR_ALT_IN_F16 | DXR_ALT_IN_BF16);
+    if (!dxr::split_out_flags(&a.radius, &a.out_flag, &a.nhwc)) return DXR_EINVAL;
+    if (a.out_flag != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return DXR_EINVAL;
+    // 16-bit fmap1 and level 0, with or without output flags
+    if (inbf) return dxr::alt_lookup_inbf16(a);
+    if (in16) return dxr::alt_lookup_in16(a);
+    if (a.out_flag != 0 || a.nhwc) return dxr::alt_lookup_out(a);
   }
-  return alt_lookup(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
-                    workspace, workspace_bytes, stream, n_levels);
+  return alt_lookup_forms<dxr::FORM_F32>(a);
 }
 }  // namespace
 
@@ -2445,4 +2367,5 @@ extern "C" int dxr_alt_corr_lookup_levels_ws(const float* fmap1, const float* co
   return alt_lookup_entry(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
                           workspace, workspace_bytes, stream, n_levels);
 }
-#endif  // DXR_ALT_INBF16_TU / DXR_ALT_IN16_TU / DXR_ALT_OUT_TU
+
+#endif  // DXR_TEMPLATES_ONLY

@@ -296,15 +296,10 @@ int alt_backward_accumulate(const float* fmap1, const float* fmap2, const float*
   if (Nc == 0) return DXR_OK;   // nothing to add
   const int b = (int)B, h1 = (int)H1, w1 = (int)W1, h2 = (int)H2, w2 = (int)W2, c = (int)C,
             nc = (int)Nc;
-  switch (r) {
-    case 0: return launch_bwd_mfma<0>(fmap1, fmap2, coords, corr_grad, fmap1_grad, fmap2_grad, b, h1, w1, h2, w2, c, nc, stream);
-    case 1: return launch_bwd_mfma<1>(fmap1, fmap2, coords, corr_grad, fmap1_grad, fmap2_grad, b, h1, w1, h2, w2, c, nc, stream);
-    case 2: return launch_bwd_mfma<2>(fmap1, fmap2, coords, corr_grad, fmap1_grad, fmap2_grad, b, h1, w1, h2, w2, c, nc, stream);
-    case 3: return launch_bwd_mfma<3>(fmap1, fmap2, coords, corr_grad, fmap1_grad, fmap2_grad, b, h1, w1, h2, w2, c, nc, stream);
-    case 4: return launch_bwd_mfma<4>(fmap1, fmap2, coords, corr_grad, fmap1_grad, fmap2_grad, b, h1, w1, h2, w2, c, nc, stream);
-    case 5: return launch_bwd_mfma<5>(fmap1, fmap2, coords, corr_grad, fmap1_grad, fmap2_grad, b, h1, w1, h2, w2, c, nc, stream);
-    default: return launch_bwd_mfma<6>(fmap1, fmap2, coords, corr_grad, fmap1_grad, fmap2_grad, b, h1, w1, h2, w2, c, nc, stream);
-  }
+  return dispatch_radius<6>(r, [&](auto rr) {
+    return launch_bwd_mfma<decltype(rr)::value>(fmap1, fmap2, coords, corr_grad, fmap1_grad,
+                                                fmap2_grad, b, h1, w1, h2, w2, c, nc, stream);
+  });
 }
 
 }  // namespace dxr

@@ -6,7 +6,10 @@
 // levels with two products instead of three — tile order and ordered, radius
 // 0..6, with and without the output flags (OUTX).  Instantiated in this
 // translation unit so that the float32-operand kernels of alt_corr.hip and
-// alt_corr_out.hip compile as they did without them.  Defines
-// dxr::alt_lookup_in16 (dxr_common.h), which the entry points call.
-#define DXR_ALT_IN16_TU
+// alt_corr_out.hip compile as they did without them.
+#define DXR_TEMPLATES_ONLY
 #include "alt_corr.hip"
+
+int dxr::alt_lookup_in16(const AltLookupArgs& a) {
+  return alt_lookup_forms<FORMS_ALL, true>(a);
+}

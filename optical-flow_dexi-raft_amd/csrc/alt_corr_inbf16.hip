@@ -7,7 +7,10 @@
 // ways, times the raw query) — tile order and ordered, radius 0..6, with and
 // without the output flags (OUTX).  Instantiated in this translation unit so that
 // the float32- and float16-operand kernels of alt_corr.hip, alt_corr_out.hip and
-// alt_corr_in16.hip compile as they did without them.  Defines
-// dxr::alt_lookup_inbf16 (dxr_common.h), which the entry points call.
-#define DXR_ALT_INBF16_TU
+// alt_corr_in16.hip compile as they did without them.
+#define DXR_TEMPLATES_ONLY
 #include "alt_corr.hip"
+
+int dxr::alt_lookup_inbf16(const AltLookupArgs& a) {
+  return alt_lookup_forms<FORMS_ALL, true, true>(a);
+}

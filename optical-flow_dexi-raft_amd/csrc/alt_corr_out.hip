@@ -4,7 +4,10 @@
 // OUTX = true, tile order and ordered, radius 0..6; the output dtype and layout
 // are a run-time switch in its last phase.  Instantiated in this translation
 // unit so that the float32 NCHW kernels of alt_corr.hip compile exactly as they
-// did without them.  Defines dxr::alt_lookup_out
-// (dxr_common.h), which the entry points call.
-#define DXR_ALT_OUT_TU
+// did without them.
+#define DXR_TEMPLATES_ONLY
 #include "alt_corr.hip"
+
+int dxr::alt_lookup_out(const AltLookupArgs& a) {
+  return alt_lookup_forms<FORMS_FLAGGED>(a);   // unflagged: alt_corr.hip's
+}

@@ -1418,33 +1418,11 @@ int launch_lookup_nhwc_r(const PT* pyr, const float* coords, OT* out, const Look
 template <typename PT, typename OT, bool NHWC = false>
 int launch_lookup(const PT* pyr, const float* coords, OT* out, const LookupGeom& g, int B,
                   int radius, hipStream_t stream) {
-  if constexpr (NHWC) {
-    switch (radius) {
-      case 0: return launch_lookup_nhwc_r<0, PT>(pyr, coords, out, g, B, stream);
-      case 1: return launch_lookup_nhwc_r<1, PT>(pyr, coords, out, g, B, stream);
-      case 2: return launch_lookup_nhwc_r<2, PT>(pyr, coords, out, g, B, stream);
-      case 3: return launch_lookup_nhwc_r<3, PT>(pyr, coords, out, g, B, stream);
-      case 4: return launch_lookup_nhwc_r<4, PT>(pyr, coords, out, g, B, stream);
-      case 5: return launch_lookup_nhwc_r<5, PT>(pyr, coords, out, g, B, stream);
-      case 6: return launch_lookup_nhwc_r<6, PT>(pyr, coords, out, g, B, stream);
-      case 7: return launch_lookup_nhwc_r<7, PT>(pyr, coords, out, g, B, stream);
-      case 8: return launch_lookup_nhwc_r<8, PT>(pyr, coords, out, g, B, stream);
-      default: return DXR_EUNSUPPORTED;
-    }
-  } else {
-  switch (radius) {
-    case 0: return launch_lookup_r<0, PT>(pyr, coords, out, g, B, stream);
-    case 1: return launch_lookup_r<1, PT>(pyr, coords, out, g, B, stream);
-    case 2: return launch_lookup_r<2, PT>(pyr, coords, out, g, B, stream);
-    case 3: return launch_lookup_r<3, PT>(pyr, coords, out, g, B, stream);
-    case 4: return launch_lookup_r<4, PT>(pyr, coords, out, g, B, stream);
-    case 5: return launch_lookup_r<5, PT>(pyr, coords, out, g, B, stream);
-    case 6: return launch_lookup_r<6, PT>(pyr, coords, out, g, B, stream);
-    case 7: return launch_lookup_r<7, PT>(pyr, coords, out, g, B, stream);
-    case 8: return launch_lookup_r<8, PT>(pyr, coords, out, g, B, stream);
-    default: return DXR_EUNSUPPORTED;
-  }
-  }
+  return dxr::dispatch_radius<8>(radius, [&](auto r) {
+    constexpr int R = decltype(r)::value;
+    if constexpr (NHWC) return launch_lookup_nhwc_r<R, PT>(pyr, coords, out, g, B, stream);
+    else return launch_lookup_r<R, PT>(pyr, coords, out, g, B, stream);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1514,27 +1492,6 @@ __device__ __forceinline__ void lk_split8h(const float (&x)[8], uint4& h, uint4&
   }
   h = make_uint4(hh[0], hh[1], hh[2], hh[3]);
   l = make_uint4(ll[0], ll[1], ll[2], ll[3]);
-}
-
-__global__ __launch_bounds__(256) void conv1x1_pack_weight_kernel(const float* __restrict__ w,
-                                                                  int cout, int cin, int kbw,
-                                                                  float4* __restrict__ packed) {
-  const int u = blockIdx.x * 256 + threadIdx.x;
-  if (u >= kbw * cout) return;
-  const int kb = u / cout, o = u - kb * cout;
-  float x[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int c = kb * 8 + e;
-    x[e] = c < cin ? w[(long long)o * cin + c] : 0.f;
-  }
-  packed[2LL * u] = make_float4(x[0], x[1], x[2], x[3]);
-  packed[2LL * u + 1] = make_float4(x[4], x[5], x[6], x[7]);
-  uint4 h, l;
-  lk_split8h(x, h, l);
-  uint4* pairs = reinterpret_cast<uint4*>(packed + 2LL * kbw * cout);
-  pairs[2LL * u] = h;
-  pairs[2LL * u + 1] = l;
 }
 
 // ---------------------------------------------------------------------------
@@ -1812,11 +1769,10 @@ template <typename PT, typename OT, bool NHWC = false>
 int launch_lookup_conv1x1(const PT* pyr, const float* coords, const float4* wpl, const float* bias,
                           OT* out, const LookupGeom& g, int B, int radius, int cout, int relu,
                           hipStream_t stream) {
-  switch (radius) {
-    case 3: return launch_lookup_conv1x1_r<3, PT, OT, NHWC>(pyr, coords, wpl, bias, out, g, B, cout, relu, stream);
-    case 4: return launch_lookup_conv1x1_r<4, PT, OT, NHWC>(pyr, coords, wpl, bias, out, g, B, cout, relu, stream);
-    default: return DXR_EUNSUPPORTED;
-  }
+  return dxr::dispatch_radius<4, 3>(radius, [&](auto r) {
+    return launch_lookup_conv1x1_r<decltype(r)::value, PT, OT, NHWC>(pyr, coords, wpl, bias, out, g, B,
+                                                                    cout, relu, stream);
+  });
 }
 
 // dxr_corr_lookup / dxr_corr_lookup_conv1x1 for one output type: the argument
@@ -1826,7 +1782,11 @@ int launch_lookup_conv1x1(const PT* pyr, const float* coords, const float4* wpl,
 // (DESIGN.md §3.11), and the float32 path is to stay the code it was.
 // NHWC (channels-last `out`): instantiated in corr_lookup_nhwc.hip only, for
 // every cell and output type.
-template <typename OT, bool NHWC = false>
+// CELLS: the pyramid cell types the including unit instantiates; a pyr_dtype
+// outside them is DXR_EINVAL (the entry points route it to its own unit first).
+enum Cells { CELLS_F32_BF16, CELLS_F16, CELLS_ALL };
+
+template <Cells CELLS, typename OT, bool NHWC = false>
 int corr_lookup_impl(const void* pyramid, int pyr_dtype, int64_t B, int64_t H, int64_t W,
                      int num_levels, int radius, const float* coords, OT* out,
                      hipStream_t stream) {
@@ -1843,24 +1803,24 @@ int corr_lookup_impl(const void* pyramid, int pyr_dtype, int64_t B, int64_t H, i
   g.levels = num_levels;
   g.cout = num_levels * rd * rd;
   for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
-#if defined(DXR_LOOKUP_PYR16_TU) || defined(DXR_LOOKUP_NHWC_TU)
-  // float16 cells: corr_lookup_pyr16.hip (and only them), corr_lookup_nhwc.hip
-  if (pyr_dtype == DXR_PYR_F16)
-    return launch_lookup<_Float16, OT, NHWC>(static_cast<const _Float16*>(pyramid), coords, out, g,
-                                             (int)B, radius, stream);
-#endif
-#ifndef DXR_LOOKUP_PYR16_TU
-  if (pyr_dtype == DXR_F32)
-    return launch_lookup<float, OT, NHWC>(static_cast<const float*>(pyramid), coords, out, g, (int)B,
-                                          radius, stream);
-  if (pyr_dtype == DXR_BF16)
-    return launch_lookup<uint16_t, OT, NHWC>(static_cast<const uint16_t*>(pyramid), coords, out, g,
-                                             (int)B, radius, stream);
-#endif
+  if constexpr (CELLS != CELLS_F32_BF16) {
+    // float16 cells: corr_lookup_pyr16.hip (and only them), corr_lookup_nhwc.hip
+    if (pyr_dtype == DXR_PYR_F16)
+      return launch_lookup<_Float16, OT, NHWC>(static_cast<const _Float16*>(pyramid), coords, out, g,
+                                               (int)B, radius, stream);
+  }
+  if constexpr (CELLS != CELLS_F16) {
+    if (pyr_dtype == DXR_F32)
+      return launch_lookup<float, OT, NHWC>(static_cast<const float*>(pyramid), coords, out, g, (int)B,
+                                            radius, stream);
+    if (pyr_dtype == DXR_BF16)
+      return launch_lookup<uint16_t, OT, NHWC>(static_cast<const uint16_t*>(pyramid), coords, out, g,
+                                               (int)B, radius, stream);
+  }
   return DXR_EINVAL;
 }
 
-template <typename OT, bool NHWC = false>
+template <Cells CELLS, typename OT, bool NHWC = false>
 int corr_lookup_conv1x1_impl(const void* pyramid, int pyr_dtype, int64_t B, int64_t H, int64_t W,
                              int num_levels, int radius, const float* coords,
                              const void* weight_packed, const float* bias, int64_t cout, int relu,
@@ -1880,23 +1840,45 @@ int corr_lookup_conv1x1_impl(const void* pyramid, int pyr_dtype, int64_t B, int6
   g.cout = num_levels * rd * rd;
   for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
   const float4* wpl = static_cast<const float4*>(weight_packed);
-#if defined(DXR_LOOKUP_PYR16_TU) || defined(DXR_LOOKUP_NHWC_TU)
-  if (pyr_dtype == DXR_PYR_F16)
-    return launch_lookup_conv1x1<_Float16, OT, NHWC>(static_cast<const _Float16*>(pyramid), coords,
-                                                     wpl, bias, out, g, (int)B, radius, (int)cout,
-                                                     relu, stream);
-#endif
-#ifndef DXR_LOOKUP_PYR16_TU
-  if (pyr_dtype == DXR_F32)
-    return launch_lookup_conv1x1<float, OT, NHWC>(static_cast<const float*>(pyramid), coords, wpl,
-                                                  bias, out, g, (int)B, radius, (int)cout, relu,
-                                                  stream);
-  if (pyr_dtype == DXR_BF16)
-    return launch_lookup_conv1x1<uint16_t, OT, NHWC>(static_cast<const uint16_t*>(pyramid), coords,
-                                                     wpl, bias, out, g, (int)B, radius, (int)cout,
-                                                     relu, stream);
-#endif
+  if constexpr (CELLS != CELLS_F32_BF16) {
+    if (pyr_dtype == DXR_PYR_F16)
+      return launch_lookup_conv1x1<_Float16, OT, NHWC>(static_cast<const _Float16*>(pyramid), coords,
+                                                       wpl, bias, out, g, (int)B, radius, (int)cout,
+                                                       relu, stream);
+  }
+  if constexpr (CELLS != CELLS_F16) {
+    if (pyr_dtype == DXR_F32)
+      return launch_lookup_conv1x1<float, OT, NHWC>(static_cast<const float*>(pyramid), coords, wpl,
+                                                    bias, out, g, (int)B, radius, (int)cout, relu,
+                                                    stream);
+    if (pyr_dtype == DXR_BF16)
+      return launch_lookup_conv1x1<uint16_t, OT, NHWC>(static_cast<const uint16_t*>(pyramid), coords,
+                                                       wpl, bias, out, g, (int)B, radius, (int)cout,
+                                                       relu, stream);
+  }
   return DXR_EINVAL;
+}
+
+// Either of the two on one argument struct (dxr_common.h): what a unit's shim
+// calls for each of its output forms.
+template <Cells CELLS, bool NHWC, typename OT>
+int pyramid_lookup(const dxr::LookupArgs& a, OT* out) {
+  if (a.conv1x1)
+    return corr_lookup_conv1x1_impl<CELLS, OT, NHWC>(a.pyramid, a.pyr_dtype, a.B, a.H, a.W,
+                                                     a.num_levels, a.radius, a.coords,
+                                                     a.weight_packed, a.bias, a.cout, a.relu, out,
+                                                     a.stream);
+  return corr_lookup_impl<CELLS, OT, NHWC>(a.pyramid, a.pyr_dtype, a.B, a.H, a.W, a.num_levels,
+                                           a.radius, a.coords, out, a.stream);
+}
+
+// A unit's whole shim: pyramid_lookup for the request's output form, FORMS being
+// the forms the unit instantiates (out_store.h).
+template <Cells CELLS, unsigned FORMS>
+int pyramid_lookup_forms(const dxr::LookupArgs& a) {
+  return dxr::dispatch_out_form<FORMS>(a.out_flag, a.nhwc, a.out, [&](auto* out, auto nhwc) {
+    return pyramid_lookup<CELLS, decltype(nhwc)::value>(a, out);
+  });
 }
 
 // The alternate block's coarse levels from their volumes (dxr_alt_coarse_volumes),
@@ -1972,173 +1954,47 @@ int alt_volume_lookup_impl(const PT* volumes, const float* coords, OT* out, int6
     g.lv[l] = level_addr(L.lay[l]);
     g.lv[l].off -= L.off[first_level];
   }
-  switch (radius) {
-    case 0: return launch_alt_volume_r<0, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 1: return launch_alt_volume_r<1, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 2: return launch_alt_volume_r<2, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 3: return launch_alt_volume_r<3, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 4: return launch_alt_volume_r<4, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 5: return launch_alt_volume_r<5, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 6: return launch_alt_volume_r<6, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 7: return launch_alt_volume_r<7, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
-    case 8: return launch_alt_volume_r<8, OT, NHWC, PT>(volumes, coords, out, g, first_level, (int)B, stream);
-    default: return DXR_EUNSUPPORTED;
-  }
+  return dxr::dispatch_radius<8>(radius, [&](auto r) {
+    return launch_alt_volume_r<decltype(r)::value, OT, NHWC, PT>(volumes, coords, out, g, first_level,
+                                                                 (int)B, stream);
+  });
+}
+
+// A unit's whole shim: alt_volume_lookup_impl on PT cells for the request's output
+// form, FORMS being the forms the unit instantiates (out_store.h).
+template <typename PT, unsigned FORMS>
+int alt_volume_lookup_forms(const dxr::AltVolumeArgs& a) {
+  return dxr::dispatch_out_form<FORMS>(a.out_flag, a.nhwc, a.out, [&](auto* out, auto nhwc) {
+    return alt_volume_lookup_impl<std::remove_pointer_t<decltype(out)>, decltype(nhwc)::value, PT>(
+        static_cast<const PT*>(a.volumes), a.coords, out, a.B, a.H, a.W, a.num_levels, a.first_level,
+        a.radius, a.divisor, a.stream);
+  });
 }
 
 }  // namespace
 
-#if defined(DXR_LOOKUP_PYR16_TU)
-// corr_lookup_pyr16.hip: this file's templates with float16 pyramid cells (every
-// output type), and nothing else of it.
-int dxr::lookup_pyr16(const void* pyramid, int out_flag, int64_t B, int64_t H, int64_t W,
-                      int num_levels, int radius, const float* coords, void* out,
-                      hipStream_t stream) {
-  if (out_flag == DXR_OUT_F16)
-    return corr_lookup_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
-                            static_cast<_Float16*>(out), stream);
-  if (out_flag == DXR_OUT_BF16)
-    return corr_lookup_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
-                            static_cast<__bf16*>(out), stream);
-  return corr_lookup_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
-                          static_cast<float*>(out), stream);
-}
-
-int dxr::lookup_conv1x1_pyr16(const void* pyramid, int out_flag, int64_t B, int64_t H, int64_t W,
-                              int num_levels, int radius, const float* coords,
-                              const void* weight_packed, const float* bias, int64_t cout, int relu,
-                              void* out, hipStream_t stream) {
-  if (out_flag == DXR_OUT_F16)
-    return corr_lookup_conv1x1_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
-                                    weight_packed, bias, cout, relu, static_cast<_Float16*>(out),
-                                    stream);
-  if (out_flag == DXR_OUT_BF16)
-    return corr_lookup_conv1x1_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
-                                    weight_packed, bias, cout, relu, static_cast<__bf16*>(out),
-                                    stream);
-  return corr_lookup_conv1x1_impl(pyramid, DXR_PYR_F16, B, H, W, num_levels, radius, coords,
-                                  weight_packed, bias, cout, relu, static_cast<float*>(out), stream);
-}
-#elif defined(DXR_LOOKUP_NHWC_TU)
-// corr_lookup_nhwc.hip: this file's templates with channels-last outputs (every
-// cell type, every output type), and nothing else of it.
-int dxr::lookup_nhwc(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H,
-                     int64_t W, int num_levels, int radius, const float* coords, void* out,
-                     hipStream_t stream) {
-  if (out_flag == DXR_OUT_F16)
-    return corr_lookup_impl<_Float16, true>(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
-                                            static_cast<_Float16*>(out), stream);
-  if (out_flag == DXR_OUT_BF16)
-    return corr_lookup_impl<__bf16, true>(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
-                                          static_cast<__bf16*>(out), stream);
-  return corr_lookup_impl<float, true>(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
-                                       static_cast<float*>(out), stream);
-}
-
-int dxr::lookup_conv1x1_nhwc(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H,
-                             int64_t W, int num_levels, int radius, const float* coords,
-                             const void* weight_packed, const float* bias, int64_t cout, int relu,
-                             void* out, hipStream_t stream) {
-  if (out_flag == DXR_OUT_F16)
-    return corr_lookup_conv1x1_impl<_Float16, true>(pyramid, pyr_dtype, B, H, W, num_levels, radius,
-                                                    coords, weight_packed, bias, cout, relu,
-                                                    static_cast<_Float16*>(out), stream);
-  if (out_flag == DXR_OUT_BF16)
-    return corr_lookup_conv1x1_impl<__bf16, true>(pyramid, pyr_dtype, B, H, W, num_levels, radius,
-                                                  coords, weight_packed, bias, cout, relu,
-                                                  static_cast<__bf16*>(out), stream);
-  return corr_lookup_conv1x1_impl<float, true>(pyramid, pyr_dtype, B, H, W, num_levels, radius,
-                                               coords, weight_packed, bias, cout, relu,
-                                               static_cast<float*>(out), stream);
-}
-#elif defined(DXR_LOOKUP_ALT_OUT_TU)
-// corr_lookup_alt_out.hip: the alternate block's volume lookup with 16-bit and / or
-// channels-last outputs, and nothing else of this file.
-int dxr::alt_volume_lookup_out(const float* volumes, const float* coords, void* out, int out_flag,
-                               bool nhwc, int64_t B, int64_t H, int64_t W, int num_levels,
-                               int first_level, int radius, float divisor, hipStream_t stream) {
-#define DXR_ALT_VOL(OT, NHWC)                                                                    \
-  alt_volume_lookup_impl<OT, NHWC>(volumes, coords, static_cast<OT*>(out), B, H, W, num_levels, \
-                                   first_level, radius, divisor, stream)
-  if (nhwc) {
-    if (out_flag == DXR_OUT_F16) return DXR_ALT_VOL(_Float16, true);
-    if (out_flag == DXR_OUT_BF16) return DXR_ALT_VOL(__bf16, true);
-    return DXR_ALT_VOL(float, true);
-  }
-  if (out_flag == DXR_OUT_F16) return DXR_ALT_VOL(_Float16, false);
-  if (out_flag == DXR_OUT_BF16) return DXR_ALT_VOL(__bf16, false);
-  return DXR_EINVAL;   // unflagged requests stay in corr_lookup.hip
-#undef DXR_ALT_VOL
-}
-#elif defined(DXR_LOOKUP_ALT_VOL16_TU)
-// corr_lookup_alt_vol16.hip: the alternate block's volume lookup on float16 volumes
-// (DXR_ALT_VOL_F16), every output form, and nothing else of this file.
-int dxr::alt_volume_lookup_vol16(const void* volumes, const float* coords, void* out, int out_flag,
-                                 bool nhwc, int64_t B, int64_t H, int64_t W, int num_levels,
-                                 int first_level, int radius, float divisor, hipStream_t stream) {
-#define DXR_ALT_VOL(OT, NHWC)                                                                      \
-  alt_volume_lookup_impl<OT, NHWC, _Float16>(static_cast<const _Float16*>(volumes), coords,        \
-                                             static_cast<OT*>(out), B, H, W, num_levels,           \
-                                             first_level, radius, divisor, stream)
-  if (nhwc) {
-    if (out_flag == DXR_OUT_F16) return DXR_ALT_VOL(_Float16, true);
-    if (out_flag == DXR_OUT_BF16) return DXR_ALT_VOL(__bf16, true);
-    return DXR_ALT_VOL(float, true);
-  }
-  if (out_flag == DXR_OUT_F16) return DXR_ALT_VOL(_Float16, false);
-  if (out_flag == DXR_OUT_BF16) return DXR_ALT_VOL(__bf16, false);
-  return DXR_ALT_VOL(float, false);
-#undef DXR_ALT_VOL
-}
-#elif defined(DXR_LOOKUP_OUT16_TU)
-// corr_lookup_out16.hip: this file's templates with the 16-bit output types, and
-// nothing else of it.
-int dxr::lookup_out16(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H,
-                      int64_t W, int num_levels, int radius, const float* coords, void* out,
-                      hipStream_t stream) {
-  if (out_flag == DXR_OUT_F16)
-    return corr_lookup_impl(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
-                            static_cast<_Float16*>(out), stream);
-  return corr_lookup_impl(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
-                          static_cast<__bf16*>(out), stream);
-}
-
-int dxr::lookup_conv1x1_out16(const void* pyramid, int pyr_dtype, int out_flag, int64_t B,
-                              int64_t H, int64_t W, int num_levels, int radius,
-                              const float* coords, const void* weight_packed, const float* bias,
-                              int64_t cout, int relu, void* out, hipStream_t stream) {
-  if (out_flag == DXR_OUT_F16)
-    return corr_lookup_conv1x1_impl(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
-                                    weight_packed, bias, cout, relu, static_cast<_Float16*>(out),
-                                    stream);
-  return corr_lookup_conv1x1_impl(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
-                                  weight_packed, bias, cout, relu, static_cast<__bf16*>(out),
-                                  stream);
-}
-#else   // the entry points (float32 outputs)
+// Everything above is templates.  The variant units (corr_lookup_*.hip) define
+// DXR_TEMPLATES_ONLY and include this file for them; what follows, the entry points
+// and what only they launch, is this unit's alone.
+#ifndef DXR_TEMPLATES_ONLY
 
 extern "C" int dxr_alt_volume_lookup(const float* volumes, const float* coords, float* out,
                                      int64_t B, int64_t H, int64_t W, int num_levels,
                                      int first_level, int radius, float divisor,
                                      hipStream_t stream) {
-  int out_flag;
-  bool nhwc;
+  dxr::AltVolumeArgs a{volumes, coords, out, 0, false, B, H, W, num_levels, first_level, radius,
+                       divisor, stream};
   // the flags on `radius` first: DXR_ALT_VOL_F16 (float16 volume cells), then the output
   // flags (DXR_OUT_F16 / DXR_OUT_BF16 / DXR_OUT_NHWC)
   if (radius >= 0) {
     const bool vol16 = (radius & DXR_ALT_VOL_F16) != 0;
-    radius &= ~DXR_ALT_VOL_F16;
-    if (!dxr::split_out_flags(&radius, &out_flag, &nhwc)) return DXR_EINVAL;
-    if (out_flag != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return DXR_EINVAL;
-    if (vol16)   // their own translation unit (corr_lookup_alt_vol16.hip)
-      return dxr::alt_volume_lookup_vol16(volumes, coords, out, out_flag, nhwc, B, H, W,
-                                          num_levels, first_level, radius, divisor, stream);
-    if (out_flag != 0 || nhwc)   // their own translation unit (corr_lookup_alt_out.hip)
-      return dxr::alt_volume_lookup_out(volumes, coords, out, out_flag, nhwc, B, H, W, num_levels,
-                                        first_level, radius, divisor, stream);
+    a.radius &= ~DXR_ALT_VOL_F16;
+    if (!dxr::split_out_flags(&a.radius, &a.out_flag, &a.nhwc)) return DXR_EINVAL;
+    if (a.out_flag != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return DXR_EINVAL;
+    if (vol16) return dxr::alt_volume_lookup_vol16(a);
+    if (a.out_flag != 0 || a.nhwc) return dxr::alt_volume_lookup_out(a);
   }
-  return alt_volume_lookup_impl(volumes, coords, out, B, H, W, num_levels, first_level, radius,
-                                divisor, stream);
+  return alt_volume_lookup_forms<float, dxr::FORM_F32>(a);
 }
 
 namespace {
@@ -2163,23 +2019,23 @@ bool split_out_dtype(int* pyr_dtype, int* out_flag, bool* nhwc, const void* out)
   *nhwc = (hi & DXR_OUT_NHWC) != 0;
   return true;
 }
+
+// dxr_corr_lookup and dxr_corr_lookup_conv1x1 after their flags: to the unit that
+// instantiates the request's form.
+int lookup_entry(dxr::LookupArgs a) {
+  if (!split_out_dtype(&a.pyr_dtype, &a.out_flag, &a.nhwc, a.out)) return DXR_EINVAL;
+  if (a.nhwc) return dxr::lookup_nhwc(a);   // channels-last: every cell and output type
+  if (a.pyr_dtype == DXR_PYR_F16) return dxr::lookup_pyr16(a);   // float16 cells: every output type
+  if (a.out_flag) return dxr::lookup_out16(a);
+  return pyramid_lookup_forms<CELLS_F32_BF16, dxr::FORM_F32>(a);
+}
 }  // namespace
 
 extern "C" int dxr_corr_lookup(const void* pyramid, int pyr_dtype, int64_t B, int64_t H,
                                int64_t W, int num_levels, int radius, const float* coords,
                                float* out, hipStream_t stream) {
-  int out_flag;
-  bool nhwc;
-  if (!split_out_dtype(&pyr_dtype, &out_flag, &nhwc, out)) return DXR_EINVAL;
-  if (nhwc)   // channels-last outputs: their own translation unit, every cell and output type
-    return dxr::lookup_nhwc(pyramid, pyr_dtype, out_flag, B, H, W, num_levels, radius, coords, out,
-                            stream);
-  if (pyr_dtype == DXR_PYR_F16)   // float16 cells: their own translation unit, every output type
-    return dxr::lookup_pyr16(pyramid, out_flag, B, H, W, num_levels, radius, coords, out, stream);
-  if (out_flag)
-    return dxr::lookup_out16(pyramid, pyr_dtype, out_flag, B, H, W, num_levels, radius, coords, out,
-                             stream);
-  return corr_lookup_impl(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords, out, stream);
+  return lookup_entry({pyramid, pyr_dtype, 0, false, B, H, W, num_levels, radius, coords, false,
+                       nullptr, nullptr, 0, 0, out, stream});
 }
 
 namespace {
@@ -2202,17 +2058,9 @@ int lookup_backward(const BwSets& sets, int64_t B, int64_t H, int64_t W, int num
   g.cout = num_levels * rd * rd;
   for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
   float* gp = static_cast<float*>(grad_pyramid);
-  switch (radius) {
-    case 0: return launch_lookup_backward_r<0>(sets, gp, g, (int)B, bound_slots, stream);
-    case 1: return launch_lookup_backward_r<1>(sets, gp, g, (int)B, bound_slots, stream);
-    case 2: return launch_lookup_backward_r<2>(sets, gp, g, (int)B, bound_slots, stream);
-    case 3: return launch_lookup_backward_r<3>(sets, gp, g, (int)B, bound_slots, stream);
-    case 4: return launch_lookup_backward_r<4>(sets, gp, g, (int)B, bound_slots, stream);
-    case 5: return launch_lookup_backward_r<5>(sets, gp, g, (int)B, bound_slots, stream);
-    case 6: return launch_lookup_backward_r<6>(sets, gp, g, (int)B, bound_slots, stream);
-    case 7: return launch_lookup_backward_r<7>(sets, gp, g, (int)B, bound_slots, stream);
-    default: return launch_lookup_backward_r<8>(sets, gp, g, (int)B, bound_slots, stream);
-  }
+  return dxr::dispatch_radius<8>(radius, [&](auto r) {
+    return launch_lookup_backward_r<decltype(r)::value>(sets, gp, g, (int)B, bound_slots, stream);
+  });
 }
 }  // namespace
 
@@ -2253,17 +2101,10 @@ extern "C" int64_t dxr_lookup_backward_bound_slots(int64_t B, int64_t H, int64_t
   g.N = (int)(H * W);
   g.levels = num_levels;
   dim3 d;
-  switch (radius) {
-    case 0: d = lookup_backward_grid<0>(g, (int)B); break;
-    case 1: d = lookup_backward_grid<1>(g, (int)B); break;
-    case 2: d = lookup_backward_grid<2>(g, (int)B); break;
-    case 3: d = lookup_backward_grid<3>(g, (int)B); break;
-    case 4: d = lookup_backward_grid<4>(g, (int)B); break;
-    case 5: d = lookup_backward_grid<5>(g, (int)B); break;
-    case 6: d = lookup_backward_grid<6>(g, (int)B); break;
-    case 7: d = lookup_backward_grid<7>(g, (int)B); break;
-    default: d = lookup_backward_grid<8>(g, (int)B); break;
-  }
+  dxr::dispatch_radius<8>(radius, [&](auto r) {
+    d = lookup_backward_grid<decltype(r)::value>(g, (int)B);
+    return DXR_OK;
+  });
   return (int64_t)d.x * d.y * d.z;
 }
 
@@ -2291,6 +2132,30 @@ extern "C" int64_t dxr_conv1x1_packed_bytes(int64_t cout, int64_t cin) {
   return ((cin + 15) / 16 * 16) * cout * 4 * 2;   // f32 copy + f16-pair copy
 }
 
+namespace {
+// dxr_conv1x1_pack_weight (layout: above, at lk_split8h).
+__global__ __launch_bounds__(256) void conv1x1_pack_weight_kernel(const float* __restrict__ w,
+                                                                  int cout, int cin, int kbw,
+                                                                  float4* __restrict__ packed) {
+  const int u = blockIdx.x * 256 + threadIdx.x;
+  if (u >= kbw * cout) return;
+  const int kb = u / cout, o = u - kb * cout;
+  float x[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int c = kb * 8 + e;
+    x[e] = c < cin ? w[(long long)o * cin + c] : 0.f;
+  }
+  packed[2LL * u] = make_float4(x[0], x[1], x[2], x[3]);
+  packed[2LL * u + 1] = make_float4(x[4], x[5], x[6], x[7]);
+  uint4 h, l;
+  lk_split8h(x, h, l);
+  uint4* pairs = reinterpret_cast<uint4*>(packed + 2LL * kbw * cout);
+  pairs[2LL * u] = h;
+  pairs[2LL * u + 1] = l;
+}
+}  // namespace
+
 extern "C" int dxr_conv1x1_pack_weight(const float* weight, int64_t cout, int64_t cin,
                                        void* packed, hipStream_t stream) {
   if (cout < 1 || cin < 1 || cout > (1 << 20) || cin > (1 << 20)) return DXR_EINVAL;
@@ -2306,20 +2171,8 @@ extern "C" int dxr_corr_lookup_conv1x1(const void* pyramid, int pyr_dtype, int64
                                        int64_t W, int num_levels, int radius, const float* coords,
                                        const void* weight_packed, const float* bias, int64_t cout,
                                        int relu, float* out, hipStream_t stream) {
-  int out_flag;
-  bool nhwc;
-  if (!split_out_dtype(&pyr_dtype, &out_flag, &nhwc, out)) return DXR_EINVAL;
-  if (nhwc)
-    return dxr::lookup_conv1x1_nhwc(pyramid, pyr_dtype, out_flag, B, H, W, num_levels, radius,
-                                    coords, weight_packed, bias, cout, relu, out, stream);
-  if (pyr_dtype == DXR_PYR_F16)
-    return dxr::lookup_conv1x1_pyr16(pyramid, out_flag, B, H, W, num_levels, radius, coords,
-                                     weight_packed, bias, cout, relu, out, stream);
-  if (out_flag)
-    return dxr::lookup_conv1x1_out16(pyramid, pyr_dtype, out_flag, B, H, W, num_levels, radius,
-                                     coords, weight_packed, bias, cout, relu, out, stream);
-  return corr_lookup_conv1x1_impl(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords,
-                                  weight_packed, bias, cout, relu, out, stream);
+  return lookup_entry({pyramid, pyr_dtype, 0, false, B, H, W, num_levels, radius, coords, true,
+                       weight_packed, bias, cout, relu, out, stream});
 }
 
-#endif  // DXR_LOOKUP_OUT16_TU
+#endif  // DXR_TEMPLATES_ONLY

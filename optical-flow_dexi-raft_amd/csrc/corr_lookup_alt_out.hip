@@ -3,7 +3,10 @@
 // form of corr_lookup.hip's corr_lookup_qm_kernel with the 16-bit and channels-
 // last stores of the product lookup.  Instantiated in this translation unit so
 // that every other kernel of corr_lookup.hip compiles exactly as it did without
-// them.  Defines dxr::alt_volume_lookup_out
-// (dxr_common.h), which the entry point calls.
-#define DXR_LOOKUP_ALT_OUT_TU
+// them.
+#define DXR_TEMPLATES_ONLY
 #include "corr_lookup.hip"
+
+int dxr::alt_volume_lookup_out(const AltVolumeArgs& a) {
+  return alt_volume_lookup_forms<float, FORMS_FLAGGED>(a);   // unflagged: corr_lookup.hip's
+}

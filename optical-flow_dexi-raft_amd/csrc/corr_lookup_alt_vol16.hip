@@ -6,7 +6,10 @@
 // flagged forms' pinned one, so every output is the float32-volume lookup of the
 // widened buffer bit for bit.  Instantiated in this translation unit so that
 // every other kernel of corr_lookup.hip compiles exactly as it did without them
-// (DESIGN.md §3.11, §3.19).  Defines dxr::alt_volume_lookup_vol16 (dxr_common.h),
-// which the entry point calls.
-#define DXR_LOOKUP_ALT_VOL16_TU
+// (DESIGN.md §3.11, §3.19).
+#define DXR_TEMPLATES_ONLY
 #include "corr_lookup.hip"
+
+int dxr::alt_volume_lookup_vol16(const AltVolumeArgs& a) {
+  return alt_volume_lookup_forms<_Float16, FORMS_ALL>(a);
+}

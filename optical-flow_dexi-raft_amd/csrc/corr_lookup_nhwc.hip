@@ -4,8 +4,10 @@
 // templates with NHWC = true: the same sums, stored along channels.  They are
 // instantiated in this translation unit so that the NCHW kernels of
 // corr_lookup.hip, corr_lookup_out16.hip and corr_lookup_pyr16.hip compile
-// exactly as they did without them.  Defines
-// dxr::lookup_nhwc and dxr::lookup_conv1x1_nhwc (dxr_common.h), which the entry
-// points call.
-#define DXR_LOOKUP_NHWC_TU
+// exactly as they did without them.
+#define DXR_TEMPLATES_ONLY
 #include "corr_lookup.hip"
+
+int dxr::lookup_nhwc(const LookupArgs& a) {
+  return pyramid_lookup_forms<CELLS_ALL, FORMS_NHWC>(a);
+}

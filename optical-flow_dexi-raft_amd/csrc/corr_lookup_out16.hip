@@ -3,7 +3,10 @@
 // The kernels are corr_lookup.hip's templates; they are instantiated in this
 // translation unit so that the float32-output kernels of corr_lookup.hip compile
 // exactly as they did without them (co-compiled, six of them
-// were allocated two more VGPRs).  Defines dxr::lookup_out16 and
-// dxr::lookup_conv1x1_out16 (dxr_common.h), which the entry points call.
-#define DXR_LOOKUP_OUT16_TU
+// were allocated two more VGPRs).
+#define DXR_TEMPLATES_ONLY
 #include "corr_lookup.hip"
+
+int dxr::lookup_out16(const LookupArgs& a) {
+  return pyramid_lookup_forms<CELLS_F32_BF16, FORMS_NCHW16>(a);
+}

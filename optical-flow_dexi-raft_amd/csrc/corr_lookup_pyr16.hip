@@ -5,7 +5,10 @@
 // float32 arithmetic after that is shared.  They are instantiated in this
 // translation unit so that the float32 / bfloat16 pyramid kernels of
 // corr_lookup.hip and corr_lookup_out16.hip compile exactly as they did without
-// them.  Defines dxr::lookup_pyr16 and
-// dxr::lookup_conv1x1_pyr16 (dxr_common.h), which the entry points call.
-#define DXR_LOOKUP_PYR16_TU
+// them.
+#define DXR_TEMPLATES_ONLY
 #include "corr_lookup.hip"
+
+int dxr::lookup_pyr16(const LookupArgs& a) {
+  return pyramid_lookup_forms<CELLS_F16, FORMS_NCHW>(a);
+}

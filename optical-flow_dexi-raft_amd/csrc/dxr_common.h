@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "dexiraft_corr.h"
 
 namespace dxr {
@@ -22,65 +24,95 @@ inline int launch_status() {
   return DXR_OK;
 }
 
-// dxr_corr_lookup / dxr_corr_lookup_conv1x1 with an output dtype flag (out_flag:
-// DXR_OUT_F16 or DXR_OUT_BF16, already split off pyr_dtype and validated; `out`
-// holds 16-bit elements).  Defined in corr_lookup_out16.hip.
-int lookup_out16(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H, int64_t W,
-                 int num_levels, int radius, const float* coords, void* out, hipStream_t stream);
-int lookup_conv1x1_out16(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H,
-                         int64_t W, int num_levels, int radius, const float* coords,
-                         const void* weight_packed, const float* bias, int64_t cout, int relu,
-                         void* out, hipStream_t stream);
+// A run-time radius in [MIN, MAX] as a std::integral_constant handed to `f`
+// (which returns a status); any other radius is DXR_EUNSUPPORTED.  `f` is
+// instantiated for exactly those radii.
+template <int MAX, int MIN = 0, typename F>
+int dispatch_radius(int radius, F&& f) {
+  if constexpr (MIN <= MAX) {
+    if (radius == MIN) return f(std::integral_constant<int, MIN>{});
+    return dispatch_radius<MAX, MIN + 1>(radius, f);
+  }
+  return DXR_EUNSUPPORTED;
+}
 
-// The same two calls on a float16 pyramid (pyr_dtype DXR_PYR_F16, split off and
-// validated by the entry points; out_flag 0: float32 `out`, else as above).
-// Defined in corr_lookup_pyr16.hip, the only translation unit that instantiates
-// the lookup kernels with the float16 cell type.
-int lookup_pyr16(const void* pyramid, int out_flag, int64_t B, int64_t H, int64_t W, int num_levels,
-                 int radius, const float* coords, void* out, hipStream_t stream);
-int lookup_conv1x1_pyr16(const void* pyramid, int out_flag, int64_t B, int64_t H, int64_t W,
-                         int num_levels, int radius, const float* coords, const void* weight_packed,
-                         const float* bias, int64_t cout, int relu, void* out, hipStream_t stream);
+// ---------------------------------------------------------------------------
+// The lookups' variant units.  A lookup's kernel forms are spread over several
+// translation units; the entry point splits and validates the
+// flags, fills one of the argument structs below and hands it to the unit that
+// instantiates the form.  out_flag: 0 (float32 `out`), DXR_OUT_F16 or
+// DXR_OUT_BF16; nhwc: DXR_OUT_NHWC (`out` is [B, H, W, C]).
+// ---------------------------------------------------------------------------
 
-// The same two calls with the layout flag DXR_OUT_NHWC (split off and validated by
-// the entry points): `out` is [B, H, W, C]; pyr_dtype DXR_F32 / DXR_BF16 /
-// DXR_PYR_F16; out_flag 0 (float32), DXR_OUT_F16 or DXR_OUT_BF16.  Defined in
-// corr_lookup_nhwc.hip, the only translation unit that instantiates the
-// channels-last forms of the lookup kernels.
-int lookup_nhwc(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H, int64_t W,
-                int num_levels, int radius, const float* coords, void* out, hipStream_t stream);
-int lookup_conv1x1_nhwc(const void* pyramid, int pyr_dtype, int out_flag, int64_t B, int64_t H,
-                        int64_t W, int num_levels, int radius, const float* coords,
-                        const void* weight_packed, const float* bias, int64_t cout, int relu,
-                        void* out, hipStream_t stream);
+// dxr_corr_lookup, and with `conv1x1` dxr_corr_lookup_conv1x1 (weight_packed,
+// bias, cout, relu).  pyr_dtype: DXR_F32 / DXR_BF16 / DXR_PYR_F16, flags off.
+struct LookupArgs {
+  const void* pyramid;
+  int pyr_dtype, out_flag;
+  bool nhwc;
+  int64_t B, H, W;
+  int num_levels, radius;
+  const float* coords;
+  bool conv1x1;
+  const void* weight_packed;
+  const float* bias;
+  int64_t cout;
+  int relu;
+  void* out;
+  hipStream_t stream;
+};
+// 16-bit NCHW outputs of float32 / bfloat16 pyramids: corr_lookup_out16.hip.
+int lookup_out16(const LookupArgs& a);
+// float16 pyramids (DXR_PYR_F16), every NCHW output type: corr_lookup_pyr16.hip,
+// the only unit that instantiates the lookup kernels with the float16 cell type.
+int lookup_pyr16(const LookupArgs& a);
+// Channels-last outputs, every cell and output type: corr_lookup_nhwc.hip.
+int lookup_nhwc(const LookupArgs& a);
 
-// The alternate block's lookups with output flags on `radius` (split off and
-// validated by the entry points; out_flag 0 / DXR_OUT_F16 / DXR_OUT_BF16, nhwc:
-// DXR_OUT_NHWC; at least one of them set).  alt_lookup_out: dxr_alt_corr_lookup,
-// _ws and _levels_ws (n_levels < 0: every level), defined in alt_corr_out.hip;
-// alt_volume_lookup_out: dxr_alt_volume_lookup, defined in
-// corr_lookup_alt_out.hip.  The only translation units that instantiate those
-// kernels' flagged forms.
-int alt_lookup_out(const float* fmap1, const float* const* fmap2_levels, const float* coords,
-                   void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W, int64_t C,
-                   int num_levels, int radius, float divisor, void* workspace,
-                   int64_t workspace_bytes, hipStream_t stream, int n_levels);
-// The same three lookups with DXR_ALT_IN_F16 on `radius` (split off by the entry
-// points, like the output flags, any of which may come with it: out_flag 0 /
-// DXR_OUT_F16 / DXR_OUT_BF16, nhwc): fmap1 and fmap2_levels[0] point at float16,
-// the further levels at float32.  Defined in alt_corr_in16.hip, the only
-// translation unit that instantiates the float16-operand forms.
-int alt_lookup_in16(const void* fmap1, const void* const* fmap2_levels, const float* coords,
-                    void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W, int64_t C,
-                    int num_levels, int radius, float divisor, void* workspace,
-                    int64_t workspace_bytes, hipStream_t stream, int n_levels);
-// The same with DXR_ALT_IN_BF16: fmap1 and fmap2_levels[0] point at bfloat16.
-// Defined in alt_corr_inbf16.hip, the only translation unit that instantiates
-// the bfloat16-operand forms.
-int alt_lookup_inbf16(const void* fmap1, const void* const* fmap2_levels, const float* coords,
-                      void* out, int out_flag, bool nhwc, int64_t B, int64_t H, int64_t W, int64_t C,
-                      int num_levels, int radius, float divisor, void* workspace,
-                      int64_t workspace_bytes, hipStream_t stream, int n_levels);
+// dxr_alt_corr_lookup, _ws and _levels_ws (n_levels < 0: every level) with the
+// flags off `radius`.  fmap1 and fmap2_levels[0] point at what the unit reads
+// (float32, float16 or bfloat16), the further levels at float32.
+struct AltLookupArgs {
+  const float* fmap1;
+  const float* const* fmap2_levels;
+  const float* coords;
+  void* out;
+  int out_flag;
+  bool nhwc;
+  int64_t B, H, W, C;
+  int num_levels, radius;
+  float divisor;
+  void* workspace;
+  int64_t workspace_bytes;
+  hipStream_t stream;
+  int n_levels;
+};
+// float32 fmaps with an output flag (at least one set): alt_corr_out.hip.
+int alt_lookup_out(const AltLookupArgs& a);
+// DXR_ALT_IN_F16, with or without output flags: alt_corr_in16.hip.
+int alt_lookup_in16(const AltLookupArgs& a);
+// DXR_ALT_IN_BF16, likewise: alt_corr_inbf16.hip.
+int alt_lookup_inbf16(const AltLookupArgs& a);
+
+// dxr_alt_volume_lookup with the flags off `radius`; `volumes` holds float32 or
+// (DXR_ALT_VOL_F16) float16 cells.
+struct AltVolumeArgs {
+  const void* volumes;
+  const float* coords;
+  void* out;
+  int out_flag;
+  bool nhwc;
+  int64_t B, H, W;
+  int num_levels, first_level, radius;
+  float divisor;
+  hipStream_t stream;
+};
+// float32 volumes with an output flag (at least one set): corr_lookup_alt_out.hip.
+int alt_volume_lookup_out(const AltVolumeArgs& a);
+// float16 volumes, every output form: corr_lookup_alt_vol16.hip, the only unit
+// that instantiates the volume lookup with the float16 cell type.
+int alt_volume_lookup_vol16(const AltVolumeArgs& a);
+
 // dxr_alt_corr_backward with DXR_ALT_BWD_ACCUMULATE on `radius` (passed whole; B,
 // the map sizes and C already checked positive, radius >= 0): validation and
 // the MFMA kernel that adds into both gradients.  Defined in alt_corr_bwd.hip.
@@ -88,16 +120,6 @@ int alt_backward_accumulate(const float* fmap1, const float* fmap2, const float*
                             const float* corr_grad, float* fmap1_grad, float* fmap2_grad,
                             int64_t B, int64_t H1, int64_t W1, int64_t H2, int64_t W2, int64_t C,
                             int64_t Nc, int radius, hipStream_t stream);
-int alt_volume_lookup_out(const float* volumes, const float* coords, void* out, int out_flag,
-                          bool nhwc, int64_t B, int64_t H, int64_t W, int num_levels,
-                          int first_level, int radius, float divisor, hipStream_t stream);
-// dxr_alt_volume_lookup with DXR_ALT_VOL_F16 on `radius` (split off by the entry point;
-// `volumes` holds float16 cells; out_flag 0 / DXR_OUT_F16 / DXR_OUT_BF16, nhwc, any
-// combination or none).  Defined in corr_lookup_alt_vol16.hip, the only translation unit
-// that instantiates the volume lookup with the float16 cell type.
-int alt_volume_lookup_vol16(const void* volumes, const float* coords, void* out, int out_flag,
-                            bool nhwc, int64_t B, int64_t H, int64_t W, int num_levels,
-                            int first_level, int radius, float divisor, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
 // Pyramid layout ("paged" correlation volume).

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "dexiraft_corr.h"
 
 namespace dxr {
@@ -144,6 +146,43 @@ inline bool split_out_flags(int* value, int* out_flag, bool* nhwc) {
   *nhwc = (hi & DXR_OUT_NHWC) != 0;
   *value &= 0xff;
   return dt == 0 || dt == DXR_OUT_F16 || dt == DXR_OUT_BF16;
+}
+
+// The six output forms (element type x layout) as a bit set: the forms a
+// translation unit may instantiate.
+enum : unsigned {
+  FORM_F32 = 1, FORM_F16 = 2, FORM_BF16 = 4,   // NCHW; channels-last: << 3
+  FORMS_NCHW = 7, FORMS_NCHW16 = FORM_F16 | FORM_BF16, FORMS_NHWC = FORMS_NCHW << 3,
+  FORMS_ALL = FORMS_NCHW | FORMS_NHWC, FORMS_FLAGGED = FORMS_ALL & ~FORM_F32
+};
+
+// A request's form (out_flag: 0, DXR_OUT_F16 or DXR_OUT_BF16) as the call
+// f(OT* out, std::bool_constant<NHWC>), OT = float / _Float16 / __bf16; `f` is
+// instantiated for the forms of FORMS only, any other form is DXR_EINVAL.
+template <unsigned FORMS, typename F>
+int dispatch_out_form(int out_flag, bool nhwc, void* out, F&& f) {
+  const unsigned dt = out_flag == DXR_OUT_F16 ? FORM_F16 : out_flag == DXR_OUT_BF16 ? FORM_BF16 : FORM_F32;
+  const unsigned form = nhwc ? dt << 3 : dt;
+  if constexpr ((FORMS & FORM_F32) != 0)
+    if (form == FORM_F32) return f(static_cast<float*>(out), std::false_type{});
+  if constexpr ((FORMS & FORM_F16) != 0)
+    if (form == FORM_F16) return f(static_cast<_Float16*>(out), std::false_type{});
+  if constexpr ((FORMS & FORM_BF16) != 0)
+    if (form == FORM_BF16) return f(static_cast<__bf16*>(out), std::false_type{});
+  if constexpr ((FORMS & FORM_F32 << 3) != 0)
+    if (form == FORM_F32 << 3) return f(static_cast<float*>(out), std::true_type{});
+  if constexpr ((FORMS & FORM_F16 << 3) != 0)
+    if (form == FORM_F16 << 3) return f(static_cast<_Float16*>(out), std::true_type{});
+  if constexpr ((FORMS & FORM_BF16 << 3) != 0)
+    if (form == FORM_BF16 << 3) return f(static_cast<__bf16*>(out), std::true_type{});
+  return DXR_EINVAL;
+}
+
+// A form as the `okind` argument of the on-the-fly kernels: 1 float16, 2 bfloat16,
+// + 4 channels-last.
+template <typename OT, bool NHWC>
+constexpr int out_kind() {
+  return (std::is_same_v<OT, _Float16> ? 1 : 0) | (std::is_same_v<OT, __bf16> ? 2 : 0) | (NHWC ? 4 : 0);
 }
 
 }  // namespace dxr
