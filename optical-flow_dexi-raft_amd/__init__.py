@@ -11,6 +11,8 @@ Public surface, mirroring the reference's interface for this path:
   * ``forward_interpolate``                — core/utils/utils.py:26-54, on the GPU
   * ``upsample_flow``                      — core/raft.py:87-98, fused, with its backward
   * ``sequence_loss``                      — train.py:48-73, fused, with its backward
+  * ``SepConvGRU``                         — core/update.py:33-60, the inference forward
+    on the matrix cores (float16 / bfloat16 operands, float32 state)
   * ``flow_metrics``                       — the EPE reductions of evaluate.py, on the GPU
   * ``driver.InputPadder / write_flo / infer_pairs`` — core/utils/utils.py:7-24,
     core/utils/frame_utils.py:70-99, evaluate.py's per-pair loop (sharded)
@@ -19,8 +21,9 @@ Public surface, mirroring the reference's interface for this path:
 from . import alt_cuda_corr, driver
 from ._native import LIB_PATH, load as load_native
 from .corr import AlternateCorrBlock, CorrBlock, TrainableAlternateCorrBlock
+from .gru import SepConvGRU
 from .utils import coords_grid, flow_metrics, forward_interpolate, sequence_loss, upsample_flow
 
-__all__ = ["CorrBlock", "AlternateCorrBlock", "TrainableAlternateCorrBlock", "alt_cuda_corr", "coords_grid", "forward_interpolate", "upsample_flow", "sequence_loss", "flow_metrics", "driver",
+__all__ = ["CorrBlock", "AlternateCorrBlock", "TrainableAlternateCorrBlock", "alt_cuda_corr", "coords_grid", "forward_interpolate", "upsample_flow", "sequence_loss", "flow_metrics", "SepConvGRU", "driver",
            "load_native", "LIB_PATH"]
 __version__ = "0.1.0"

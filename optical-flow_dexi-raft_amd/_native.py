@@ -136,8 +136,28 @@ LOSS_SIGNATURES: dict[str, tuple[object, list[object]]] = {
                                           _vp, _i64, _i64, _i64, _f64, _f32, _vp]),
 }
 
+# Every symbol include/dexiraft_gru.h declares (prefix dxg_, its own ABI version), in a
+# shared object of their own, libdexiraft_gru.so, which depends on libdexiraft_corr.so.
+GRU_LIB_PATH = LIB_PATH.with_name("libdexiraft_gru.so")
+GRU_ABI_VERSION = 1
+DXG_F32, DXG_F16, DXG_BF16 = 0, 1, 2   # enum dxg_dtype
+_g5 = [_i64, _i64, _i64, _i64, _i64]   # N, H, W, Ch, Cx
+GRU_SIGNATURES: dict[str, tuple[object, list[object]]] = {
+    "dxg_abi_version": (_int, []),
+    "dxg_sepconv_packed_weight_bytes": (_i64, [_i64, _i64]),
+    "dxg_sepconv_pack_weights": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _i64,
+                                        _vp]),
+    "dxg_sepconv_workspace_bytes": (_i64, _g5),
+    "dxg_sepconv_pack_inputs": (_int, [_vp, _int, _vp, _int, *_g5, _int, _vp, _i64, _vp]),
+    "dxg_sepconv_gate_zr": (_int, [_vp, _int, *_g5, _int, _vp, _i64, _vp]),
+    "dxg_sepconv_gate_qh": (_int, [_vp, _int, *_g5, _int, _vp, _int, _vp, _i64, _vp]),
+    "dxg_sepconv_gru": (_int, [_vp, _int, _vp, _int, _vp, _vp, *_g5, _int, _vp, _int, _vp, _i64,
+                               _vp]),
+}
+
 _lock = threading.Lock()
 _lib: ctypes.CDLL | None = None
+_gru_lib: ctypes.CDLL | None = None
 
 
 def load() -> ctypes.CDLL:
@@ -175,6 +195,31 @@ def load() -> ctypes.CDLL:
                                   "rebuild")
             _lib = lib
     return _lib
+
+
+def load_gru() -> ctypes.CDLL:
+    """Load (once) and return libdexiraft_gru.so, after the library it depends on."""
+    global _gru_lib
+    if _gru_lib is not None:
+        return _gru_lib
+    load()
+    with _lock:
+        if _gru_lib is None:
+            if not GRU_LIB_PATH.exists():
+                raise ImportError(
+                    f"{GRU_LIB_PATH.name} not found next to {Path(__file__).name}; build it with "
+                    "`python optical-flow_dexi-raft_amd/build.py` (hipcc, gfx950)")
+            lib = ctypes.CDLL(str(GRU_LIB_PATH))
+            for name, (res, args) in GRU_SIGNATURES.items():
+                fn = getattr(lib, name)
+                fn.restype = res
+                fn.argtypes = args
+            ver = lib.dxg_abi_version()
+            if ver != GRU_ABI_VERSION:
+                raise ImportError(f"{GRU_LIB_PATH.name} ABI {ver} != expected {GRU_ABI_VERSION}; "
+                                  "rebuild")
+            _gru_lib = lib
+    return _gru_lib
 
 
 def check(status: int, what: str) -> None:

@@ -1,9 +1,13 @@
-"""Build libdexiraft_corr.so (HIP, gfx950) in-tree.
+"""Build libdexiraft_corr.so and libdexiraft_gru.so (HIP, gfx950) in-tree.
 
 Every ``csrc/*.hip`` file is compiled with ``hipcc --offload-arch=gfx950`` into
 ``build/*.o`` and linked into ``libdexiraft_corr.so`` next to this file, so the
 shared object travels with the repository snapshot to the GPU box.  No torch
 headers are involved: the library is a plain C-ABI (include/dexiraft_corr.h).
+The ``csrc/gru_*.hip`` files (include/dexiraft_gru.h, prefix dxg_) are linked into
+a second shared object, ``libdexiraft_gru.so``, which depends on the first (for
+``dxr_last_hip_error``): the export list of ``libdexiraft_corr.so`` stays the four
+ABIs it has always been.
 
 Usage: ``python optical-flow_dexi-raft_amd/build.py [--force] [--asm]``.
 """
@@ -25,6 +29,7 @@ INCLUDE = REPO_DIR / "include"
 BUILD_DIR = PKG_DIR / "build"
 LIB_NAME = "libdexiraft_corr.so"
 LIB_PATH = PKG_DIR / LIB_NAME
+GRU_LIB_PATH = PKG_DIR / "libdexiraft_gru.so"
 # Experiments target (timing ablations; never loaded by the package): the
 # csrc/experiments/*.hip files, each of which includes the product source it
 # varies, objects in build/exp.
@@ -46,8 +51,12 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found: the HIP toolchain (/opt/rocm) is required to build")
 
 
+def _gru_sources() -> list[Path]:
+    return sorted(CSRC.glob("gru_*.hip"))
+
+
 def _sources(experiments: bool = False) -> list[Path]:
-    product = sorted(CSRC.glob("*.hip"))
+    product = [p for p in sorted(CSRC.glob("*.hip")) if not p.name.startswith("gru_")]
     if not experiments:
         return product
     # Each experiment #includes the product source it varies and so stands in for
@@ -58,14 +67,15 @@ def _sources(experiments: bool = False) -> list[Path]:
 
 
 def _deps(experiments: bool = False) -> list[Path]:
-    deps = _sources() + sorted(CSRC.glob("*.h")) + sorted(INCLUDE.glob("*.h")) + [Path(__file__)]
+    deps = _sources() + _gru_sources() + sorted(CSRC.glob("*.h")) + sorted(INCLUDE.glob("*.h")) + [Path(__file__)]
     return deps + (_sources(True) if experiments else [])
 
 
 def is_stale(lib: Path = LIB_PATH) -> bool:
-    if not lib.exists():
+    libs = [lib] if lib == EXP_LIB_PATH else [lib, GRU_LIB_PATH]
+    if not all(p.exists() for p in libs):
         return True
-    t = lib.stat().st_mtime
+    t = min(p.stat().st_mtime for p in libs)
     return any(p.stat().st_mtime > t for p in _deps(lib == EXP_LIB_PATH))
 
 
@@ -107,17 +117,26 @@ def build(force: bool = False, asm: bool = False, verbose: bool = False,
     srcs = _sources(experiments)
     if not srcs:
         raise RuntimeError(f"no sources in {EXP_DIR if experiments else CSRC}")
-    with cf.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
-        objs = list(ex.map(lambda s: _compile(s, extra, out_dir), srcs))
+    gru_srcs = [] if experiments else _gru_sources()
+    with cf.ThreadPoolExecutor(max_workers=min(8, len(srcs) + len(gru_srcs))) as ex:
+        objs = list(ex.map(lambda s: _compile(s, extra, out_dir), srcs + gru_srcs))
+    _link(lib, objs[:len(srcs)], [], verbose)
+    if gru_srcs:
+        # resolved against libdexiraft_corr.so in the same directory at load time
+        _link(GRU_LIB_PATH, objs[len(srcs):],
+              [f"-L{PKG_DIR}", f"-l:{LIB_NAME}", "-Wl,-rpath,$ORIGIN"], verbose)
+    return lib
+
+
+def _link(lib: Path, objs: list[Path], extra: list[str], verbose: bool) -> None:
     tmp = lib.with_suffix(".so.tmp")
-    cmd = [hipcc(), "-shared", f"--offload-arch={ARCH}", "-o", str(tmp), *map(str, objs)]
+    cmd = [hipcc(), "-shared", f"--offload-arch={ARCH}", "-o", str(tmp), *map(str, objs), *extra]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError(f"link failed:\n{' '.join(cmd)}\n{res.stderr}")
     os.replace(tmp, lib)
     if verbose:
         print(f"built {lib}")
-    return lib
 
 
 if __name__ == "__main__":
