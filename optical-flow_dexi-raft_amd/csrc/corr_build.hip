@@ -39,8 +39,27 @@ constexpr int NTGT = TH * TW;    // 128 targets per workgroup
 constexpr int WAVES = 4;         // waves split the 128 queries of a page
 constexpr int BM = 32 * WAVES;   // = dxr::PAGE_Q
 constexpr int NT = 64 * WAVES;
-constexpr int P0 = NTGT + 4;     // LDS pitch (floats) of a staged level-0 query row
+// Level-0 staging of the paged epilogue: per round a wave stages four level-0
+// rows (4 * TW floats, two MFMA tiles) of each of its 32 queries at pitch PQ0.
+// In 16-byte units the pitch is 17:
+//  - ds_write_b128 is served in groups of 8 consecutive lanes, each lane taking
+//    4 of the 32 banks: lanes j .. j + 7 of a group (same lane half, same row
+//    and column quad) sit at units 17 j + const, i.e. j mod 8: all distinct.
+//  - ds_read_b128 is served in four groups of 16 lanes that each span the 64
+//    banks, and a group mixes quarters of the wave (lanes {0-3, 12-15, 20-27},
+//    {4-11, 16-19, 28-31} and the same + 32).  Lanes that read different
+//    queries in one group must therefore see the same unit offset mod 16: with
+//    17 units per query, queries 16 apart do (17 * 16 = 0 mod 16), so the
+//    read-back pairs query q with q + 16 within each half of the wave (f32:
+//    16 lanes per query and round; 16-bit outputs: 8 lanes per query, two
+//    reads each, and the second pair of queries one unit on, which interleaves
+//    its even units with the first pair's odd ones).
+// (A pitch of 16 units would serialise the stores 8-way; round 5's 2 x 2
+// experiment read query q beside q + 1 at this pitch, a 2-way conflict.)
+constexpr int PQ0 = 4 * TW + 4;  // LDS pitch (floats) of a query's four staged level-0 rows
 constexpr int P1 = 32 + 4;       // LDS pitch of a staged level-1 query block
+constexpr int WSTAGE = 32 * PQ0; // floats of a wave's private staging region
+static_assert(32 * P1 <= WSTAGE, "the level-1 block fits the staging region");
 static_assert(BM == dxr::PAGE_Q, "one workgroup = one page");
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -253,10 +272,21 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 // f32 values of the level above, in the reference's window order
 // ((v00+v01)+v10)+v11 (F.avg_pool2d), then rounded to OT once.
 // `wave`: which 32 queries of the page this wave holds (and its private LDS
-// staging region).
+// staging region, WSTAGE floats at lds + wave * WSTAGE).
+// Level 0 goes through that region in two rounds of one tile pair each: round
+// r stages MFMA tiles 2r and 2r + 1 of all 32 queries, i.e. level-0 rows
+// 4r .. 4r + 3 (acc[t][c] of lane (j, h) is row 2t + h, col c of query j) —
+// 256 contiguous bytes (f32) of each query's 512-byte page slice.  Every lane
+// issues 8 unmasked 16-byte LDS stores per round, and each 1 KiB global store
+// instruction reads back four queries' quarter-KiB runs (16-bit outputs: eight
+// queries' 128-byte lines), whole 128-byte lines all.  (Until round 23 a round
+// staged all four tiles of 16 queries under an EXEC mask: 32 half-empty LDS
+// stores per wave.)  Bank layout: PQ0 above.
 // EX: bit 0 syncs only the wave around its private staging region instead of
 // the workgroup; bit 1 streams the pyramid with non-temporal stores; bit 2 with
-// write-through (sc1) buffer stores.
+// write-through (sc1) buffer stores.  Bit 3 (experiments target only, a timing
+// ablation): the level-0 staging stores are skipped and the level-0 global
+// stores write whatever the staging region holds.
 template <int EX>
 __device__ __forceinline__ void epi_sync() {
   if constexpr ((EX & 1) != 0) {
@@ -313,38 +343,38 @@ __device__ __forceinline__ float paged_epilogue(f32x16 (&acc)[4], float* lds, OT
                                                 const BuildGeom& g, long long page, int wave,
                                                 int lane) {
   const int j = lane & 31, h = lane >> 5;
-  float* wl = lds + wave * 16 * P0;   // this wave's private LDS region
+  float* wl = lds + wave * WSTAGE;   // this wave's private LDS region
 
-  // Level 0: 16 queries per round staged as [q][8][16] f32 rows, then streamed
-  // as 1 KiB wave stores.
+  // Level 0: per round rows 4r .. 4r + 3 of all 32 queries staged as [q][4][16]
+  // f32, then streamed as 1 KiB wave stores (query q beside q + 16: PQ0).
   OT* const pb0 = pyr + g.loff[0] + page * (BM * NTGT);   // page bases (workgroup-uniform)
   OT* pg0 = pb0 + (long long)wave * 32 * NTGT;
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
-    if ((j >> 4) == r) {
-      float* row = wl + (j & 15) * P0 + h * TW;
+    if constexpr ((EX & 8) == 0) {
+      float* row = wl + j * PQ0 + h * TW;
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
+      for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int c4 = 0; c4 < 4; ++c4)
-          st4(row + 2 * t * TW + 4 * c4, acc[t][4 * c4], acc[t][4 * c4 + 1],
-              acc[t][4 * c4 + 2], acc[t][4 * c4 + 3]);
+          st4(row + 2 * s * TW + 4 * c4, acc[2 * r + s][4 * c4], acc[2 * r + s][4 * c4 + 1],
+              acc[2 * r + s][4 * c4 + 2], acc[2 * r + s][4 * c4 + 3]);
     }
     epi_sync<EX>();
     if constexpr (sizeof(OT) == 4) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        const int qq = 2 * k + (lane >> 5);
-        const int off = (lane & 31) * 4;
-        { const float4 x = f4(wl + qq * P0 + off);
-          epi_put<EX>(pb0, pg0 + (r * 16 + qq) * NTGT + off, f32x4v{x.x, x.y, x.z, x.w}); }
+        const int qq = 2 * k + (lane >> 5) + 16 * ((lane >> 4) & 1);
+        const int off = (lane & 15) * 4;
+        { const float4 x = f4(wl + qq * PQ0 + off);
+          epi_put<EX>(pb0, pg0 + qq * NTGT + r * (4 * TW) + off, f32x4v{x.x, x.y, x.z, x.w}); }
       }
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const int qq = 4 * k + (lane >> 4);
-        const int off = (lane & 15) * 8;
-        store8<OT, EX>(pb0, pg0 + (r * 16 + qq) * NTGT + off, wl + qq * P0 + off);
+        const int qq = 4 * k + (lane >> 4) + 16 * ((lane >> 3) & 1);
+        const int off = (lane & 7) * 8;
+        store8<OT, EX>(pb0, pg0 + qq * NTGT + r * (4 * TW) + off, wl + qq * PQ0 + off);
       }
     }
     epi_sync<EX>();
@@ -447,7 +477,7 @@ __device__ __forceinline__ float paged_epilogue(f32x16 (&acc)[4], float* lds, OT
 // only, row-major [B*N][H][W] (CorrBlock.corr's [B,H,W,1,H,W] volume).
 template <int BK>
 constexpr int build_lds_floats() {
-  return 2 * BK * (BM + NTGT) > WAVES * 16 * P0 ? 2 * BK * (BM + NTGT) : WAVES * 16 * P0;
+  return 2 * BK * (BM + NTGT) > WAVES * WSTAGE ? 2 * BK * (BM + NTGT) : WAVES * WSTAGE;
 }
 
 // One page (128 queries x one 8x16 target tile of pair b): K loop + epilogue.
@@ -613,7 +643,7 @@ template <bool VEC, typename OT, bool DIV, int MINW, bool REMAP = false>
 __global__ __launch_bounds__(NT, MINW) void corr_build_bf16_kernel(const uint16_t* __restrict__ f1,
                                                              const uint16_t* __restrict__ f2,
                                                              OT* __restrict__ pyr, BuildGeom g) {
-  constexpr int LDS_E = WAVES * 16 * P0 * 4;          // epilogue bytes
+  constexpr int LDS_E = WAVES * WSTAGE * 4;          // epilogue bytes
   constexpr int LDS_K = 2 * STAGE_H * 2;              // two stages, bytes
   __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_K > LDS_E ? LDS_K : LDS_E];
   uint16_t* lh = reinterpret_cast<uint16_t*>(smem);
@@ -770,7 +800,7 @@ template <typename OT, bool DIV, int MINW, bool NHWC = false>
 __global__ __launch_bounds__(2 * NT, MINW) void corr_build_bf16_q2_kernel(
     const uint16_t* __restrict__ f1, const uint16_t* __restrict__ f2, OT* __restrict__ pyr,
     BuildGeom g) {
-  constexpr int LDS_E = 2 * WAVES * 16 * P0 * 4;   // epilogue bytes (8 waves)
+  constexpr int LDS_E = 2 * WAVES * WSTAGE * 4;   // epilogue bytes (8 waves)
   constexpr int LDS_K = 2 * STAGE_Q2 * 2;          // two stages, bytes
   __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_K > LDS_E ? LDS_K : LDS_E];
   uint16_t* lh = reinterpret_cast<uint16_t*>(smem);
@@ -897,7 +927,7 @@ __global__ __launch_bounds__(2 * NT, MINW) void corr_build_bf16_q2_kernel(
   // 606 us; the 1.13 GB pyramid outgrows the caches anyway; write-through sc1
   // stores are slower here: step 1,258 -> 1,345 us)
   constexpr int EX = 3;
-  paged_epilogue<OT, EX>(acc, reinterpret_cast<float*>(smem) + half * WAVES * 16 * P0, pyr, g, page,
+  paged_epilogue<OT, EX>(acc, reinterpret_cast<float*>(smem) + half * WAVES * WSTAGE, pyr, g, page,
                          w4, lane);
 }
 
@@ -1021,7 +1051,7 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float*
                                                                     const float* __restrict__ f2,
                                                                     OT* __restrict__ pyr,
                                                                     BuildGeom g) {
-  constexpr int LDS_E = WAVES * 16 * P0 * 4;                         // epilogue bytes
+  constexpr int LDS_E = WAVES * WSTAGE * 4;                         // epilogue bytes
   constexpr int LDS_K = 2 * 3 * (NHWC ? NTGT * 24 : PLANE_S) * 2;     // two stages, bytes
   __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_K > LDS_E ? LDS_K : LDS_E];
   __shared__ int redo;  // H2: some accumulator of the page is not finite
@@ -1480,7 +1510,7 @@ constexpr int DMA_LDS_BYTES = DMA_LDS_RING + NTGT * 4;
 // Tail quarter units (dma_tail_split): the exchange region (two 32-query groups
 // x four 32-target tiles of accumulators) and the epilogue staging after it.
 constexpr int DMA_XS_BYTES = 2 * 4 * 16 * 64 * 4;
-static_assert(DMA_XS_BYTES + WAVES * 16 * P0 * 4 <= DMA_LDS_RING, "tail exchange + staging fit");
+static_assert(DMA_XS_BYTES + WAVES * WSTAGE * 4 <= DMA_LDS_RING, "tail exchange + staging fit");
 
 // Unscale, divide by sqrt(D) and write one wave's 32 queries x 8x16 targets
 // (f32 build), then — if the wave saw a non-finite sum — recompute them on
@@ -1768,7 +1798,7 @@ __global__ __launch_bounds__(2 * NT, 4) void corr_build_dma_kernel(
     const uint8_t* __restrict__ sp1, const uint8_t* __restrict__ sp2, const int* __restrict__ ex1,
     const int* __restrict__ ex2, OT* __restrict__ pyr, const float* __restrict__ f1,
     const float* __restrict__ f2, int ps, int ks, int pstr, int kstr, BuildGeom g) {
-  static_assert(WAVES * 16 * P0 * 4 * 2 <= DMA_LDS_RING, "the epilogue staging aliases the ring");
+  static_assert(WAVES * WSTAGE * 4 * 2 <= DMA_LDS_RING, "the epilogue staging aliases the ring");
   constexpr bool BF = OPK != DMA_PAIRS;   // record operands: 32 channels per stage, no scales
   // one LDS array (cdna_hip_programming.md §5 item 4(a))
   __shared__ __attribute__((aligned(16))) unsigned char smem[DMA_LDS_BYTES];
@@ -1908,7 +1938,7 @@ __global__ __launch_bounds__(2 * NT, 4) void corr_build_dma_kernel(
   __builtin_amdgcn_s_barrier();   // ring reads done: the LDS is free for reuse
   const bool live = pc.qblk + half < g.qt;            // this half's query block exists
   const long long page = pc.page + (live ? (long long)half * g.tiles_h * g.tiles_w : 0);
-  float* const stage = reinterpret_cast<float*>(smem) + half * WAVES * 16 * P0;
+  float* const stage = reinterpret_cast<float*>(smem) + half * WAVES * WSTAGE;
   if constexpr (BF) {
     if (live) {
       scale_acc<DIV>(acc, g);
@@ -2234,8 +2264,8 @@ bool dma_stream_out(const BuildGeom& g, int B) {
 }
 
 // Launch corr_build_dma_kernel<OT, DIV, OPK, EXF> with DIV from g.recip and EXF
-// from dma_stream_out.
-template <typename OT, int OPK, typename... A>
+// from dma_stream_out (| EXA: the experiments target's epilogue ablation bits).
+template <typename OT, int OPK, int EXA = 0, typename... A>
 void launch_dma_kernel(const dim3& rg, const BuildGeom& g, int B, hipStream_t stream, A... args) {
   const bool so = dma_stream_out<OT>(g, B);
   auto go = [&](auto div_tag, auto ex_tag) {
@@ -2244,8 +2274,8 @@ void launch_dma_kernel(const dim3& rg, const BuildGeom& g, int B, hipStream_t st
     hipLaunchKernelGGL((corr_build_dma_kernel<OT, DV, OPK, EXF>), rg, dim3(2 * NT), 0, stream,
                        args..., g);
   };
-  using T5 = std::integral_constant<int, 5>;
-  using T3 = std::integral_constant<int, 3>;
+  using T5 = std::integral_constant<int, 5 | EXA>;
+  using T3 = std::integral_constant<int, 3 | EXA>;
   if (g.recip == 0.f) {
     if (so) go(std::true_type{}, T3{});
     else go(std::true_type{}, T5{});
@@ -2259,7 +2289,7 @@ void launch_dma_kernel(const dim3& rg, const BuildGeom& g, int B, hipStream_t st
 // (dxr::dma_workspace_bytes, build_plan.h).
 using dxr::align256;
 
-template <bool NHWC, typename OT>
+template <bool NHWC, int EXA = 0, typename OT>
 int launch_dma(const float* f1, const float* f2, OT* pyr, BuildGeom g, int B, void* ws,
                hipStream_t stream, int tail = DMA_TAIL_DEFAULT) {
   const long long N = g.N, spb = align256((long long)B * g.D * N * 4), eb = align256((long long)B * N * 4);
@@ -2279,7 +2309,7 @@ int launch_dma(const float* f1, const float* f2, OT* pyr, BuildGeom g, int B, vo
   if (st != DXR_OK) return st;
   const dim3 rg = dma_grid(g, B, stream, tail);
   const int ps = NHWC ? g.D : 1, ks = NHWC ? 1 : g.N;   // fallback operand strides
-  launch_dma_kernel<OT, DMA_PAIRS>(rg, g, B, stream, (const uint8_t*)sp1, (const uint8_t*)sp2,
+  launch_dma_kernel<OT, DMA_PAIRS, EXA>(rg, g, B, stream, (const uint8_t*)sp1, (const uint8_t*)sp2,
                                (const int*)e1, (const int*)e2, pyr, f1, f2, ps, ks, 64, g.N * 64);
   return dxr::launch_status();
 }
@@ -2287,13 +2317,13 @@ int launch_dma(const float* f1, const float* f2, OT* pyr, BuildGeom g, int B, vo
 // 16-bit operand records by LDS-DMA (corr_build_dma_kernel<.., OPK>, OPK =
 // DMA_BF16 or DMA_F16): channels-last bf16 / f16 fmaps are read in place (pixel
 // stride D * 2 B, stage stride 64 B).
-template <int OPK = DMA_BF16, typename OT>
+template <int OPK = DMA_BF16, int EXA = 0, typename OT>
 int launch_dma_bf16_nhwc(const uint16_t* f1, const uint16_t* f2, OT* pyr, BuildGeom g, int B,
                          hipStream_t stream, int tail = DMA_TAIL_DEFAULT) {
   const dim3 rg = dma_grid(g, B, stream, tail);
   const uint8_t* a = reinterpret_cast<const uint8_t*>(f1);
   const uint8_t* c = reinterpret_cast<const uint8_t*>(f2);
-  launch_dma_kernel<OT, OPK>(rg, g, B, stream, a, c, (const int*)nullptr, (const int*)nullptr, pyr,
+  launch_dma_kernel<OT, OPK, EXA>(rg, g, B, stream, a, c, (const int*)nullptr, (const int*)nullptr, pyr,
                               (const float*)nullptr, (const float*)nullptr, 0, 0, g.D * 2, 64);
   return dxr::launch_status();
 }

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(2 * NT, 4) void xp_build_dma_kernel(
   }
   const unsigned long long xt0 = (XP & 256) ? __builtin_amdgcn_s_memrealtime() : 0ull;
   constexpr int LDS_RING = DMA_RING * DMA_STAGE;
-  constexpr int LDS_E = 2 * WAVES * 16 * P0 * 4;          // epilogue staging (8 waves)
+  constexpr int LDS_E = 2 * WAVES * WSTAGE * 4;          // epilogue staging (8 waves)
   static_assert(LDS_E <= LDS_RING, "the epilogue staging aliases the ring");
   // one LDS array (cdna_hip_programming.md §5 item 4(a)): ring | target
   // exponents (128 int) | redo flag
@@ -270,13 +270,13 @@ __global__ __launch_bounds__(2 * NT, 4) void xp_build_dma_kernel(
           for (int r = 0; r < 16; ++r) sum += acc[t][r];
         if (sum == 1234.5f) pyr[tid] = to_out<OT>(sum);  // keeps the K loop live
       } else if constexpr ((XP & 64) != 0) {   // non-temporal instead of write-through stores
-        paged_epilogue<OT, 1 | 2>(acc, reinterpret_cast<float*>(smem) + half * WAVES * 16 * P0,
+        paged_epilogue<OT, 1 | 2>(acc, reinterpret_cast<float*>(smem) + half * WAVES * WSTAGE,
                                   pyr, g, page, w4, lane);
       } else if constexpr ((XP & 128) != 0) {  // plain (write-back) stores
-        paged_epilogue<OT, 1>(acc, reinterpret_cast<float*>(smem) + half * WAVES * 16 * P0,
+        paged_epilogue<OT, 1>(acc, reinterpret_cast<float*>(smem) + half * WAVES * WSTAGE,
                               pyr, g, page, w4, lane);
       } else {
-        paged_epilogue<OT, 1 | 4>(acc, reinterpret_cast<float*>(smem) + half * WAVES * 16 * P0,
+        paged_epilogue<OT, 1 | 4>(acc, reinterpret_cast<float*>(smem) + half * WAVES * WSTAGE,
                                   pyr, g, page, w4, lane);
       }
     }
@@ -521,7 +521,7 @@ __global__ __launch_bounds__(2 * NT, 4) void xp_build_persist_kernel(
     }
     if (live) {
       scale_acc<false>(acc, g);
-      paged_epilogue<OT, 1 | 4>(acc, reinterpret_cast<float*>(smem) + half * WAVES * 16 * P0, pyr,
+      paged_epilogue<OT, 1 | 4>(acc, reinterpret_cast<float*>(smem) + half * WAVES * WSTAGE, pyr,
                                 g, page, w4, lane);
     }
     if constexpr ((XP & 256) != 0) {
@@ -601,7 +601,9 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t page_rsrc(OT* base, int elems,
 // Part PART of paged_epilogue for one wave (same arithmetic and order):
 // 0 / 1 level-0 queries 0-15 / 16-31 of the wave, 2 levels 1-3.  `wl` is the
 // wave's private staging region (16 x P0 floats), `w4` its 32 queries' slot in
-// the page.
+// the page.  (The level-0 staging is the product's of rounds 4 to 22: 16
+// queries x all four tiles per part, whole query rows at pitch P0.)
+constexpr int P0 = NTGT + 4;     // LDS pitch (floats) of a staged level-0 query row
 template <typename OT, int AUX, int PART>
 __device__ __forceinline__ void pipe_epilogue_part(const f32x16 (&acc)[4], float* wl, OT* pyr,
                                                    const BuildGeom& g, long long page, int w4,
@@ -1161,6 +1163,30 @@ extern "C" int dxr_xp_build_tail(const void* f1, const void* f2, int in_dtype, i
                                 static_cast<uint16_t*>(pyr), g, (int)B, stream, tail);
   return launch_dma_bf16_nchw(static_cast<const uint16_t*>(f1), static_cast<const uint16_t*>(f2),
                               static_cast<uint16_t*>(pyr), g, (int)B, ws, stream, tail);
+}
+
+// The product's DMA builds (kernel, grid, tail and store policy as launched by
+// the package) with an epilogue ablation: nostage = 1 skips only the level-0
+// LDS staging stores (paged_epilogue EX bit 3; the level-0 global stores then
+// write whatever the staging region holds — timing only), 0 is the product.
+// f32 NCHW (ws as dxr_corr_pyramid_build_ws) or bf16 channels-last (no workspace).
+extern "C" int dxr_xp_build_epi(const void* f1, const void* f2, int in_dtype, int64_t B, int64_t D,
+                                int64_t H, int64_t W, void* pyr, void* ws, int nostage,
+                                hipStream_t stream) {
+  dxr::Levels L;
+  if (!dxr::make_levels(B, H, W, 4, &L)) return DXR_EINVAL;
+  const BuildGeom g = make_geom(D, H, W, std::sqrt((float)D), L);
+  if (in_dtype == DXR_F32) {
+    const float* a = static_cast<const float*>(f1);
+    const float* c = static_cast<const float*>(f2);
+    return nostage ? launch_dma<false, 8>(a, c, static_cast<float*>(pyr), g, (int)B, ws, stream)
+                   : launch_dma<false>(a, c, static_cast<float*>(pyr), g, (int)B, ws, stream);
+  }
+  const uint16_t* a = static_cast<const uint16_t*>(f1);
+  const uint16_t* c = static_cast<const uint16_t*>(f2);
+  return nostage ? launch_dma_bf16_nhwc<DMA_BF16, 8>(a, c, static_cast<uint16_t*>(pyr), g, (int)B,
+                                                     stream)
+                 : launch_dma_bf16_nhwc(a, c, static_cast<uint16_t*>(pyr), g, (int)B, stream);
 }
 
 // ---------------------------------------------------------------------------

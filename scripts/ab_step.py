@@ -10,7 +10,9 @@ and times interleaved rounds of replays (HIP events, after a clock warm-up):
   --block corr  build (product CorrBlock; variant -4: the --prev-lib library's
                 dxr_corr_pyramid_build_ws, product lookups; -5: the --prev-lib library's
                 build and lookups, for A/Bs across a pyramid-layout change; -6: the experiments
-                target's DMA build, product lookups) + 12 lookups by dxr_xp_lookup variant
+                target's DMA build, product lookups; -7 and -8: the --prev-lib2 library's build
+                through the same call as -4, twice — two libraries' builds on one code path
+                with a null pair beside them) + 12 lookups by dxr_xp_lookup variant
                 (libdexiraft_corr_exp.so: 0 spatial level-2/3 gathers, 32 query-major,
                 64 the 256 x 16 shape, 128 1024 x 64) or the product's (-1);
   --block alt   12 on-the-fly lookups: dxr_alt_corr_lookup (-1, tile order),
@@ -52,6 +54,8 @@ def main():
     ap.add_argument("--prev-lib", default=str(REPO / "scripts" / "libdexiraft_corr_r04.so"),
                     help="variant -3: dxr_corr_lookup of this earlier product library; "
                          "-4: its build")
+    ap.add_argument("--prev-lib2", default=None,
+                    help="variants -7 and -8: this library's build (as -4 runs --prev-lib's)")
     a = ap.parse_args()
     import dexiraft_amd
     from dexiraft_amd import _native as nat
@@ -76,6 +80,13 @@ def main():
             if hasattr(prev, name):
                 getattr(prev, name).restype = res
                 getattr(prev, name).argtypes = args
+    prev2 = None
+    if -7 in a.variants or -8 in a.variants:
+        prev2 = ctypes.CDLL(a.prev_lib2)
+        for name, (res, args) in nat.SIGNATURES.items():
+            if hasattr(prev2, name):
+                getattr(prev2, name).restype = res
+                getattr(prev2, name).argtypes = args
     dev = torch.device("cuda", 0)
     B, (H, W), D = a.batch, SHAPES[a.workload], 256
     g = torch.Generator(device=dev)
@@ -129,8 +140,8 @@ def main():
                                              o.data_ptr(), s)
                     assert st == 0
             elif a.block == "corr":
-                if v == -4:   # the previous library's build into the same buffer
-                    st = prev.dxr_corr_pyramid_build_ws(
+                if v in (-4, -7, -8):   # another library's build into the same buffer
+                    st = (prev if v == -4 else prev2).dxr_corr_pyramid_build_ws(
                         f1.data_ptr(), f2.data_ptr(), cb._in_dt, nat.DXR_NCHW, B, D, H, W, 4,
                         float(D) ** 0.5, cb._buf.data_ptr(), cb._pyr_dt, nat.DXR_BUILD_AUTO,
                         bws.data_ptr(), nb, s)
@@ -138,7 +149,7 @@ def main():
                     f_1, f_2, st = cb._launch_build(f1, f2)
                 assert st == 0
                 for c, o in zip(coords, outs):
-                    if v in (-1, -3, -4):
+                    if v in (-1, -3, -4, -7, -8):
                         fn = prev.dxr_corr_lookup if v == -3 else lib.dxr_corr_lookup
                         st = fn(cb._buf.data_ptr(), cb._pyr_dt, B, H, W, 4, 4, c.data_ptr(),
                                 o.data_ptr(), s)
