@@ -441,6 +441,18 @@ int dxr_corr_lookup_backward_multi_bound(const float* const* coords,
  * f32 class (f16 pair split of both operands, x = hi + 2^-11 lo, three MFMA
  * products, f32 accumulation; workgroups whose sums are not finite re-run it on
  * the exact three-way bf16 split).
+ * Range: the split carries no power-of-two prescale.  hi = f16(x) and
+ * lo = f16((x - hi) * 2048) represent an operand (weight or sample) to 2^-22 |x|
+ * while |x| >= 2^-13, and to an absolute 2^-36 below that (f16's subnormal
+ * grid): the contraction is f32 class while operand magnitudes are at least
+ * 2^-13; a smaller operand contributes up to 2^-36 times the other operand's
+ * magnitude per product.  Magnitudes of 65520 and above round to inf in f16, make
+ * the sums non-finite and take the workgroup (32 consecutive queries of one batch
+ * item) to the bf16 split, which has float32's range.  Per output element,
+ * |out - exact| <= sum_c [d(|w|) d(|x|) + e(|w|) |x| + |w| e(|x|)]
+ *                  + (cin + 4) 2^-24 (|bias| + sum_c |w| |x|),
+ * d(a) = 2^-11 a (2^-25 below 2^-14), e(a) = 2^-11 d(a)
+ * (tests/motion_oracle.py, tests/test_gpu_motion_per_element.py).
  *   weight_packed : dxr_conv1x1_pack_weight of the [cout, cin] float32 weight,
  *                   cin = num_levels*(2r+1)^2 (dxr_conv1x1_packed_bytes bytes:
  *                   float32 [ceil(cin/16)*2][cout][8], zero padded, followed by

@@ -805,7 +805,14 @@ class CorrBlock:
         elements in a channels-last tensor, stored so by the kernel (as
         ``__call__``).
         The samples are bit-identical to ``__call__``'s; the contraction runs in
-        f32 class on the matrix cores.  Inference only (raises under grad for
+        f32 class on the matrix cores while operand magnitudes (weights and
+        samples) are at least 2^-13: both are split into float16 pairs without a
+        prescale, so a smaller operand is carried with an absolute resolution of
+        2^-36 instead of a relative 2^-22.  A workgroup (32 consecutive pixels of
+        one batch item) whose sums are not finite, e.g. because an operand of
+        65520 or more is inf in float16, repeats its contraction on a three-way
+        bfloat16 split with float32's range.  The per-element bound is derived in
+        tests/motion_oracle.py.  Inference only (raises under grad for
         inputs that require grad).  Supported: radius 3/4, num_levels <= 4,
         Cout a multiple of 32 (the reference's 256 and 96).
         """
