@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256) void alt_corr_kernel(const float* __restrict__
 // query's own window.  Every fmap2 cell vector is then read once per workgroup
 // instead of once per query (the per-query form above re-reads 100 cell vectors
 // per query: 6.7 GB per 1080p lookup, 1.37 ms).  f32 class: both operands are
-// split into f16 pairs (H2, as the split build, csrc/corr_build.hip; r01: a 3-way
+// split into f16 pairs (as the split build, csrc/corr_build.hip; r01: a 3-way
 // bf16 split with six products, still the overflow fallback) and accumulated in
 // f32; the query planes are split once into LDS, cell vectors in registers as
 // they arrive (one k step ahead).  Box
@@ -208,6 +208,7 @@ typedef __bf16 abf2 __attribute__((ext_vector_type(2)));
 typedef float af2 __attribute__((ext_vector_type(2)));
 
 constexpr int TQY = 4, TQX = 8, TQ = TQY * TQX;    // query tile (32 pixels)
+constexpr int ALT_MFMA_C = 256;                    // channels the query planes hold (C <= 256)
 
 __device__ __forceinline__ uint32_t alt_cvt_pk(float a, float b) {
   const af2 v = {a, b};
@@ -255,8 +256,8 @@ __device__ __forceinline__ void alt_split8h(const float (&x)[8], uint4& h, uint4
   l = make_uint4(ll[0], ll[1], ll[2], ll[3]);
 }
 
-// H2: the f16 pair split (3 f16 products, cross terms in a second accumulator),
-// as the split build; a chunk whose sums are not finite (an operand beyond f16
+// The f16 pair split (3 f16 products, cross terms in a second accumulator), as
+// the split build; a chunk whose sums are not finite (an operand beyond f16
 // range, or inf/NaN) is recomputed by its wave on the 3-way bf16 split, with
 // the query operand split from fmap1 in registers.
 // BIN: the workgroup's 32 queries are not a 4 x 8 pixel tile but 32 consecutive
@@ -311,9 +312,8 @@ __device__ __forceinline__ void alt_split8h(const float (&x)[8], uint4& h, uint4
 //     (tl q, tm q, th q: small terms first), no query parts; inf and NaN go
 //     through the split as in the float32 form's fallback, so no second pass.
 // Without INBF no statement of it is compiled.
-template <int R, int NRB, int CMAX, bool H2 = false, int MINW = 2, bool BIN = false, int PF = 1,
-          int DMA = 0, int XP = 0, bool FULL = false, bool OUTX = false, bool IN16 = false,
-          bool INBF = false>
+template <int R, int MINW = 2, bool BIN = false, int PF = 1, int DMA = 0, int XP = 0,
+          bool FULL = false, bool OUTX = false, bool IN16 = false, bool INBF = false>
 __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* __restrict__ f1,
                                                                const float* __restrict__ coords,
                                                                float* __restrict__ out,
@@ -322,12 +322,16 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
                                                                long long ord_stride, int XL,
                                                                int okind) {
   static_assert(!OUTX || (!FULL && XP == 0), "flagged outputs: the product lookup only");
-  static_assert(!IN16 || (H2 && !FULL && XP == 0 && DMA == 0), "float16 fmaps: the product lookup only");
+  static_assert(!IN16 || (!FULL && XP == 0 && DMA == 0), "float16 fmaps: the product lookup only");
   static_assert(!INBF || IN16, "bfloat16 fmaps: a kind of the 16-bit operand form");
   constexpr int RD = 2 * R + 1, RD1 = RD + 1, NCELL = RD1 * RD1;
+  // 32-cell blocks per wave and chunk.  Always 1 (the DMA forms stage one block
+  // per wave); the [NRB] arrays and rb loops below stay as they are because
+  // flattening them changes the register allocation of every instantiation.
+  constexpr int NRB = 1;
   constexpr int CHUNK = 4 * 32 * NRB;                       // box cells per chunk
-  constexpr int KB = CMAX / 8;                              // 8-channel blocks
-  constexpr int NPL = IN16 ? 1 : H2 ? 2 : 3;                // query operand planes
+  constexpr int KB = ALT_MFMA_C / 8;                        // 8-channel blocks
+  constexpr int NPL = IN16 ? 1 : 2;                         // query operand planes
   // (IN16 with OUTX: at least the channels-last stage of the last phase, which one
   // plane does not hold from r = 6)
   constexpr int QPU = (IN16 && OUTX && TQ * (RD * RD | 1) * 4 > NPL * KB * TQ * 16)
@@ -349,7 +353,7 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // Workgroups are dealt round-robin to the 8 XCDs; XCD k takes the k-th
   // contiguous band of tiles instead, so neighbouring tiles (whose boxes overlap)
-  // share one L2 (the bijection of csrc/corr_build.hip's page_coord; r01 1080p:
+  // share one L2 (the bijection of csrc/corr_build.hip's banded_coord; r01 1080p:
   // FETCH 424 -> 162 MB per lookup).  XL (levels dividing 8, levels x tiles a
   // multiple of 8): the XCDs are shared out by level too — 8 / levels XCDs per
   // level, each taking a contiguous band of that level's list — so one output
@@ -471,18 +475,10 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
     const float4 a = *reinterpret_cast<const float4*>(src);
     const float4 c = *reinterpret_cast<const float4*>(src + 4);
     const float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-    if constexpr (H2) {
-      uint4 h, l;
-      alt_split8h(x, h, l);
-      qplanes[(0 * KB + kb) * TQ + qq] = h;
-      qplanes[(1 * KB + kb) * TQ + qq] = l;
-    } else {
-      uint4 h, m, l;
-      alt_split8(x, h, m, l);
-      qplanes[(0 * KB + kb) * TQ + qq] = h;
-      qplanes[(1 * KB + kb) * TQ + qq] = m;
-      qplanes[(2 * KB + kb) * TQ + qq] = l;
-    }
+    uint4 h, l;
+    alt_split8h(x, h, l);
+    qplanes[(0 * KB + kb) * TQ + qq] = h;
+    qplanes[(1 * KB + kb) * TQ + qq] = l;
   }
   __syncthreads();
 
@@ -518,7 +514,6 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
     // (row j, pieces 4 step + 2 kh, + 1) are conflict-free ds_read_b128.  Same operands, same
     // split, same products in the same order: bit-identical to the register form.
     auto kloop_dma = [&]() {
-      static_assert(NRB == 1, "the DMA form stages one 32-cell block per wave");
       af16 acc2 = {};
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[0][r] = 0.f;
@@ -583,7 +578,6 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
     // so the fragment reads (row j, pieces 2 kh, 2 kh + 1) are conflict-free
     // ds_read_b128.  Same operands, split and products: bit-identical.
     auto kloop_dma2 = [&]() {
-      static_assert(NRB == 1, "the DMA form stages one 32-cell block per wave");
       constexpr int NS = 4;
       af16 acc2 = {};
 #pragma unroll
@@ -714,7 +708,7 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
           abf8 qh, qm, ql;
           if constexpr (INBF) {   // the raw bfloat16 query row is the B operand of all three
             qh = __builtin_bit_cast(abf8, qplanes[(2 * ks + kh) * TQ + j]);
-          } else if constexpr (H2 && IN16) {   // fallback: the float16 query row, widened here
+          } else if constexpr (IN16) {   // fallback: the float16 query row, widened here
             const ah8 u = *reinterpret_cast<const ah8*>(qsrch + ks * 16);
             const float x[8] = {(float)u[0], (float)u[1], (float)u[2], (float)u[3],
                                 (float)u[4], (float)u[5], (float)u[6], (float)u[7]};
@@ -723,7 +717,7 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
             qh = __builtin_bit_cast(abf8, h);
             qm = __builtin_bit_cast(abf8, m);
             ql = __builtin_bit_cast(abf8, l);
-          } else if constexpr (H2) {     // fallback: split the query operand here
+          } else {     // fallback: split the query operand here
             const float4 u = *reinterpret_cast<const float4*>(qsrc + ks * 16);
             const float4 w = *reinterpret_cast<const float4*>(qsrc + ks * 16 + 4);
             const float x[8] = {u.x, u.y, u.z, u.w, w.x, w.y, w.z, w.w};
@@ -732,10 +726,6 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
             qh = __builtin_bit_cast(abf8, h);
             qm = __builtin_bit_cast(abf8, m);
             ql = __builtin_bit_cast(abf8, l);
-          } else {
-            qh = __builtin_bit_cast(abf8, qplanes[(0 * KB + 2 * ks + kh) * TQ + j]);
-            qm = __builtin_bit_cast(abf8, qplanes[(1 * KB + 2 * ks + kh) * TQ + j]);
-            ql = __builtin_bit_cast(abf8, qplanes[(2 * KB + 2 * ks + kh) * TQ + j]);
           }
 #pragma unroll
           for (int rb = 0; rb < NRB; ++rb) {
@@ -826,11 +816,11 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
           for (int r = 0; r < 16; ++r) bad |= !(__builtin_fabsf(acc[rb][r]) <= 3.40282347e38f);
         if (__ballot(bad) != 0) kloop(std::integral_constant<bool, false>{});   // wave-uniform
       }
-    } else if constexpr (H2) {
-      if constexpr (DMA == 2 && NRB == 1) {
+    } else {
+      if constexpr (DMA == 2) {
         if (nkb % 2 == 0) kloop_dma2();
         else kloop(std::integral_constant<bool, true>{});
-      } else if constexpr (DMA == 1 && NRB == 1) {
+      } else if constexpr (DMA == 1) {
         if (nkb % 4 == 0) kloop_dma();
         else kloop(std::integral_constant<bool, true>{});
       } else {
@@ -843,8 +833,6 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
         for (int r = 0; r < 16; ++r) bad |= !(__builtin_fabsf(acc[rb][r]) <= 3.40282347e38f);
       if ((XP & 13) == 0 && __ballot(bad) != 0)
         kloop(std::integral_constant<bool, false>{});   // wave-uniform
-    } else {
-      kloop(std::integral_constant<bool, false>{});
     }
     if constexpr (FULL) {
       // every sum of query j to its row of the volume: D rows (r & 3) + 8 (r >> 2)
@@ -1297,7 +1285,7 @@ constexpr int alt_minwbf(int r) { return r >= 6 ? 3 : 4; }
 // OUTX / okind: the flagged output forms (alt_corr_mfma_kernel), tile order and ordered.
 // IN16: float16 fmap1 and the float16 levels of g.f16_levels (alt_corr_in16.hip).
 // INBF (with IN16): they are bfloat16 (alt_corr_inbf16.hip).
-template <int R, int NRB, int DMA = 0, int PF = 4, int XP = 0, bool OUTX = false, bool IN16 = false,
+template <int R, int DMA = 0, int PF = 4, int XP = 0, bool OUTX = false, bool IN16 = false,
           bool INBF = false>
 int launch_alt_mfma_r(const float* f1, const float* coords, float* out, const AltGeom& g,
                       int levels, int Z, int W1, hipStream_t stream, void* ws = nullptr,
@@ -1312,7 +1300,7 @@ int launch_alt_mfma_r(const float* f1, const float* coords, float* out, const Al
   const int xl_ok = (8 % levels == 0 && ((long long)levels * ntiles) % 8 == 0) ? 1 : 0;
   const int XL = xl < 0 ? 0 : (xl & xl_ok);
   const dim3 grid((unsigned)ntiles, (unsigned)levels, (unsigned)Z);
-  if (g.C > 256) return DXR_EUNSUPPORTED;
+  if (g.C > ALT_MFMA_C) return DXR_EUNSUPPORTED;
   // f16 pair split (r02, 1080p: 227 vs 275 us for the 3-way bf16 split), 3 workgroups/CU
   if (ws != nullptr && Z <= 65535) {
     OrderArgs o;
@@ -1341,32 +1329,32 @@ int launch_alt_mfma_r(const float* f1, const float* coords, float* out, const Al
     // indexes int4 entries by ((z * levels + l) * np + i), so lists are laid out
     // with a stride of list_bytes / 16 entries
     if constexpr (DMA != 0)
-      hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, 2, true, 1, DMA>), grid,
+      hipLaunchKernelGGL((alt_corr_mfma_kernel<R, 2, true, 1, DMA>), grid,
                          dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x,
                          reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL, 0);
     else if constexpr (INBF)
-      hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minwbf(R), true, PF, 0, 0, false, OUTX, true, true>),
+      hipLaunchKernelGGL((alt_corr_mfma_kernel<R, alt_minwbf(R), true, PF, 0, 0, false, OUTX, true, true>),
                          grid, dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x,
                          reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL, okind);
     else if constexpr (IN16)
-      hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw16(R), true, PF, 0, 0, false, OUTX, true>),
+      hipLaunchKernelGGL((alt_corr_mfma_kernel<R, alt_minw16(R), true, PF, 0, 0, false, OUTX, true>),
                          grid, dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x,
                          reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL, okind);
     else
-      hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw(R), true, PF, 0, XP, false, OUTX>),
+      hipLaunchKernelGGL((alt_corr_mfma_kernel<R, alt_minw(R), true, PF, 0, XP, false, OUTX>),
                          grid, dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x,
                          reinterpret_cast<const int4*>(ws), o.list_bytes / 16, XL, okind);
     return dxr::launch_status();
   }
   if constexpr (INBF)
-    hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minwbf(R), false, 1, 0, 0, false, OUTX, true, true>), grid,
+    hipLaunchKernelGGL((alt_corr_mfma_kernel<R, alt_minwbf(R), false, 1, 0, 0, false, OUTX, true, true>), grid,
                        dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x, nullptr, 0, 0, okind);
   else if constexpr (IN16)
-    hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw16(R), false, 1, 0, 0, false, OUTX, true>), grid,
+    hipLaunchKernelGGL((alt_corr_mfma_kernel<R, alt_minw16(R), false, 1, 0, 0, false, OUTX, true>), grid,
                        dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x, nullptr, 0, 0, okind);
   else
-  hipLaunchKernelGGL((alt_corr_mfma_kernel<R, NRB, 256, true, alt_minw(R), false, 1, 0, 0, false, OUTX>), grid,
-                     dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x, nullptr, 0, 0, okind);
+    hipLaunchKernelGGL((alt_corr_mfma_kernel<R, alt_minw(R), false, 1, 0, 0, false, OUTX>), grid,
+                       dim3(256), 0, stream, f1, coords, out, g, W1, tiles_x, nullptr, 0, 0, okind);
   return dxr::launch_status();
 }
 
@@ -1393,9 +1381,9 @@ int launch_alt(const float* f1, const float* coords, float* out, const AltGeom& 
   // MFMA form: C a multiple of 16 (k16 steps) up to 256, 16-byte aligned rows;
   // the per-query VALU form otherwise.  With a workspace (`ord`) the queries are
   // ordered first (alt_bin_*_kernel).
-  if (vec && W1 > 0 && g.C % 16 == 0 && g.C <= 256)
+  if (vec && W1 > 0 && g.C % 16 == 0 && g.C <= ALT_MFMA_C)
     return dxr::dispatch_radius<6>(radius, [&](auto r) {
-      return launch_alt_mfma_r<decltype(r)::value, 1, 0, 4, 0, OUTX, IN16, INBF>(
+      return launch_alt_mfma_r<decltype(r)::value, 0, 4, 0, OUTX, IN16, INBF>(
           f1, coords, out, g, levels, Z, W1, stream, ord, -1, okind);
     });
   if constexpr (OUTX || IN16) return DXR_EUNSUPPORTED;
@@ -1844,7 +1832,7 @@ __global__ __launch_bounds__(256, 2) void alt_volume_gemm_kernel(
   const int j = lane & 31, kh = lane >> 5;
   const int wc = wave & 1, wq = wave >> 1;     // the wave's 64-cell / 64-query half
   // contiguous bands of (query block, cell group) per XCD (csrc/corr_build.hip's
-  // page_coord bijection): one XCD's workgroups share their query block's operand in L2
+  // banded_coord bijection): one XCD's workgroups share their query block's operand in L2
   const int n = gridDim.x, q8 = n / 8, r8 = n % 8, xcd = (int)blockIdx.x % 8;
   const int idx = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) +
                   (int)blockIdx.x / 8;
@@ -2267,7 +2255,7 @@ int alt_coarse_volumes(const float* fmap1, const float* const* fmap2_levels, int
       if (st != DXR_OK) return st;
       continue;
     }
-    hipLaunchKernelGGL((alt_corr_mfma_kernel<0, 1, 256, true, 3, false, 4, 0, 0, true>),
+    hipLaunchKernelGGL((alt_corr_mfma_kernel<0, 3, false, 4, 0, 0, true>),
                        dim3((unsigned)ntiles, 1u, (unsigned)B), dim3(256), 0, stream, fmap1,
                        (const float*)nullptr, volumes, g, (int)W, tiles_x, (const int4*)nullptr,
                        0LL, 0, 0);

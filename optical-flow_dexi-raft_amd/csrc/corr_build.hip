@@ -78,8 +78,9 @@ struct BuildGeom {
                         // rest quarter units of the tail (dma_tail_split)
 };
 
-// Page coordinates of this workgroup.  3-D grid (tiles, query blocks, pairs), or
-// with REMAP a 1-D grid laid out for the per-XCD L2s: workgroup w runs on XCD
+// Page coordinates of this workgroup.  3-D grid (tiles, query blocks, pairs:
+// grid_coord), or a 1-D grid laid out for the per-XCD L2s (banded_coord, QB = 2
+// query blocks per workgroup): workgroup w runs on XCD
 // w % 8 (round-robin dispatch; used for speed only), the bijective remap of
 // cdna_hip_programming.md §5 gives each XCD a contiguous range of a linear
 // order, and that order walks strips of STRIP target tiles query-block-major,
@@ -125,32 +126,30 @@ __device__ __forceinline__ PageCoord unit_coord(const BuildGeom& g, long long wl
   return c;
 }
 
-template <bool REMAP, int QB = 1>
-__device__ __forceinline__ PageCoord page_coord(const BuildGeom& g) {
-  if constexpr (REMAP) {
-    const long long nwg = (long long)min((unsigned)g.nmain, gridDim.x);
-    const long long w = blockIdx.x;
-    const long long q8 = nwg / 8, r8 = nwg % 8, xcd = w % 8;
-    const long long wl = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + w / 8;
-    return unit_coord<QB>(g, wl);
-  } else {
-    PageCoord c;
-    c.txi = blockIdx.x % g.tiles_w;
-    c.tyi = blockIdx.x / g.tiles_w;
-    c.qblk = blockIdx.y * QB;
-    c.b = blockIdx.z;
-    c.page = (((long long)c.b * g.qt + c.qblk) * g.tiles_h + c.tyi) * g.tiles_w + c.txi;
-    return c;
-  }
+__device__ __forceinline__ PageCoord banded_coord(const BuildGeom& g) {
+  const long long nwg = (long long)min((unsigned)g.nmain, gridDim.x);
+  const long long w = blockIdx.x;
+  const long long q8 = nwg / 8, r8 = nwg % 8, xcd = w % 8;
+  const long long wl = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + w / 8;
+  return unit_coord<2>(g, wl);
+}
+
+__device__ __forceinline__ PageCoord grid_coord(const BuildGeom& g) {
+  PageCoord c;
+  c.txi = blockIdx.x % g.tiles_w;
+  c.tyi = blockIdx.x / g.tiles_w;
+  c.qblk = blockIdx.y;
+  c.b = blockIdx.z;
+  c.page = (((long long)c.b * g.qt + c.qblk) * g.tiles_h + c.tyi) * g.tiles_w + c.txi;
+  return c;
 }
 
 // Global -> register staging of one BK slice of the query panel (A: [BK][BM])
 // and the target tile (B: [BK][TH][TW]).  VEC: W % 4 == 0, so every float4 is
 // fully inside or fully outside the map; outside elements stage as zero.
-// NHWC (scalar form only): channels-last fmaps [H*W][D].
-template <bool VEC, int BK, bool NHWC = false>
+constexpr int BK = 16;           // K per stage of the exact-f32 build
+template <bool VEC>
 struct Stage {
-  static_assert(!(VEC && NHWC), "channels-last staging is scalar");
   static constexpr int NA = VEC ? BK * BM / 4 / NT : BK * BM / NT;    // per-thread units
   static constexpr int NB = VEC ? BK * NTGT / 4 / NT : BK * NTGT / NT;
   static_assert(NA >= 1 && NB >= 1, "tile too small for the thread count");
@@ -175,7 +174,7 @@ struct Stage {
         const int k = idx / BM, c = idx % BM;
         const int kk = k0 + k, q = q0 + c;
         a[s] = (kk < g.D && q < g.N)
-                   ? f1b[NHWC ? (long long)q * g.D + kk : (long long)kk * g.N + q] : 0.f;
+                   ? f1b[(long long)kk * g.N + q] : 0.f;
       }
     }
 #pragma unroll
@@ -192,8 +191,7 @@ struct Stage {
         const int k = idx >> 7, r = (idx >> 4) & 7, c = idx & 15;
         const int kk = k0 + k, hh = th0 + r, ww = tw0 + c;
         const long long p = (long long)hh * g.W + ww;
-        b[s] = (kk < g.D && hh < g.H && ww < g.W) ? f2b[NHWC ? p * g.D + kk : kk * g.N + p]
-                                                  : 0.f;
+        b[s] = (kk < g.D && hh < g.H && ww < g.W) ? f2b[kk * g.N + p] : 0.f;
       }
     }
   }
@@ -475,7 +473,6 @@ __device__ __forceinline__ float paged_epilogue(f32x16 (&acc)[4], float* lds, OT
 
 // PAGED: write the paged pyramid (levels 1..4 fused).  !PAGED: write level 0
 // only, row-major [B*N][H][W] (CorrBlock.corr's [B,H,W,1,H,W] volume).
-template <int BK>
 constexpr int build_lds_floats() {
   return 2 * BK * (BM + NTGT) > WAVES * WSTAGE ? 2 * BK * (BM + NTGT) : WAVES * WSTAGE;
 }
@@ -500,7 +497,7 @@ __device__ __forceinline__ void scale_acc(f32x16 (&acc)[4], const BuildGeom& g) 
 
 // `tid`: the thread's index among the page's NT threads (its workgroup may hold
 // several such groups, each with its own `lds` region, running in step).
-template <bool VEC, int BK, bool PAGED, typename OT, bool DIV, bool NHWC = false>
+template <bool VEC, bool PAGED, typename OT, bool DIV>
 __device__ __forceinline__ void build_page_f32(const float* __restrict__ f1,
                                                const float* __restrict__ f2,
                                                OT* __restrict__ pyr, const BuildGeom& g,
@@ -552,7 +549,7 @@ __device__ __forceinline__ void build_page_f32(const float* __restrict__ f1,
     }
   };
   {
-    Stage<VEC, BK, NHWC> st;
+    Stage<VEC> st;
     st.load(f1b, f2b, 0, q0, th0, tw0, g, tid);
     st.store(As(0), Bs(0), tid);
     __syncthreads();
@@ -598,14 +595,14 @@ __device__ __forceinline__ void build_page_f32(const float* __restrict__ f1,
 // the f32 reference the split build is tested against (DXR_BUILD_EXACT_F32).
 // One page per workgroup (grid = TX*TY x QT x B).  MINW = waves per SIMD the
 // register allocation must allow (0 = compiler's choice).
-template <bool VEC, int BK, bool PAGED, typename OT, int MINW, bool DIV>
+template <bool VEC, bool PAGED, typename OT, int MINW, bool DIV>
 __global__ __launch_bounds__(NT, MINW) void corr_build_f32_kernel(const float* __restrict__ f1,
                                                             const float* __restrict__ f2,
                                                             OT* __restrict__ pyr, BuildGeom g) {
-  __shared__ float lds[build_lds_floats<BK>()];
+  __shared__ float lds[build_lds_floats()];
   const long long page =
       ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-  build_page_f32<VEC, BK, PAGED, OT, DIV>(f1, f2, pyr, g, lds, page, (int)threadIdx.x);
+  build_page_f32<VEC, PAGED, OT, DIV>(f1, f2, pyr, g, lds, page, (int)threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -639,7 +636,7 @@ __device__ __forceinline__ int tgt_col(int r, int c) {
   return (r >> 1) * 32 + (c & 3) + 4 * (r & 1) + 8 * (c >> 2);
 }
 
-template <bool VEC, typename OT, bool DIV, int MINW, bool REMAP = false>
+template <typename OT, bool DIV, int MINW>
 __global__ __launch_bounds__(NT, MINW) void corr_build_bf16_kernel(const uint16_t* __restrict__ f1,
                                                              const uint16_t* __restrict__ f2,
                                                              OT* __restrict__ pyr, BuildGeom g) {
@@ -649,7 +646,7 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_bf16_kernel(const uint16_
   uint16_t* lh = reinterpret_cast<uint16_t*>(smem);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const PageCoord pc = page_coord<REMAP>(g);
+  const PageCoord pc = grid_coord(g);
   const int txi = pc.txi, tyi = pc.tyi;
   const int th0 = tyi * TH, tw0 = txi * TW;
   const int q0 = pc.qblk * BM;
@@ -664,75 +661,34 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_bf16_kernel(const uint16_
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
-  // Staging units: VEC = 4 bf16 (8 B) per unit, 4 units per thread per image,
-  // read with buffer loads (per-lane byte offsets fixed over the K loop, the
-  // stage's k offset in an SGPR; units past the query count, off the image or
-  // past D fall outside the resource and read zeros).  Host side guarantees
-  // D * N * 2 < 2^31 for VEC.
-  uint2 ra[4], rb[4];
+  // Staging: 16 single elements per thread per image; elements past the query
+  // count, off the image or past D stage as zero.
   uint16_t sa[16], sb[16];
-  uint32_t voa[4], vob[4];
-  __amdgpu_buffer_rsrc_t rsa, rsb;
-  if constexpr (VEC) {
-    rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(f1b), (short)0, g.D * g.N * 2,
-                                            0x00020000);
-    rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(f2b), (short)0, g.D * g.N * 2,
-                                            0x00020000);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int idx = tid + NT * s;
-      const int k = idx >> 5;
-      const int q = q0 + (idx & 31) * 4;
-      voa[s] = q < g.N ? (uint32_t)(k * g.N + q) * 2u : 0x80000000u;
-      const int r = (idx >> 2) & 7, c = (idx & 3) * 4, hh = th0 + r, ww = tw0 + c;
-      vob[s] = (hh < g.H && ww < g.W) ? (uint32_t)(k * g.N + hh * g.W + ww) * 2u : 0x80000000u;
-    }
-  }
   auto load = [&](int k0) {
-    if constexpr (VEC) {
-      const int so = k0 * g.N * 2;
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        ra[s] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rsa, voa[s], so, 0));
-        rb[s] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rsb, vob[s], so, 0));
+    for (int s = 0; s < 16; ++s) {
+      const int idx = tid + NT * s;
+      const int k = idx >> 7, kk = k0 + k;
+      {
+        const int q = q0 + (idx & 127);
+        sa[s] = (kk < g.D && q < g.N) ? f1b[(long long)kk * g.N + q] : (uint16_t)0;
       }
-    } else {
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        const int idx = tid + NT * s;
-        const int k = idx >> 7, kk = k0 + k;
-        {
-          const int q = q0 + (idx & 127);
-          sa[s] = (kk < g.D && q < g.N) ? f1b[(long long)kk * g.N + q] : (uint16_t)0;
-        }
-        {
-          const int r = (idx >> 4) & 7, c = idx & 15, hh = th0 + r, ww = tw0 + c;
-          sb[s] = (kk < g.D && hh < g.H && ww < g.W) ? f2b[(long long)kk * g.N + hh * g.W + ww]
-                                                     : (uint16_t)0;
-        }
+      {
+        const int r = (idx >> 4) & 7, c = idx & 15, hh = th0 + r, ww = tw0 + c;
+        sb[s] = (kk < g.D && hh < g.H && ww < g.W) ? f2b[(long long)kk * g.N + hh * g.W + ww]
+                                                   : (uint16_t)0;
       }
     }
   };
   auto store = [&](int buf) {
     uint16_t* A = lh + buf * STAGE_H;
     uint16_t* Bt = A + BKH * PH;
-    if constexpr (VEC) {
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int idx = tid + NT * s;
-        const int k = idx >> 5;
-        *reinterpret_cast<uint2*>(A + k * PH + (idx & 31) * 4) = ra[s];
-        const int r = (idx >> 2) & 7, c = (idx & 3) * 4;
-        *reinterpret_cast<uint2*>(Bt + k * PH + tgt_col(r, c)) = rb[s];
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        const int idx = tid + NT * s;
-        const int k = idx >> 7;
-        A[k * PH + (idx & 127)] = sa[s];
-        Bt[k * PH + tgt_col((idx >> 4) & 7, idx & 15)] = sb[s];
-      }
+    for (int s = 0; s < 16; ++s) {
+      const int idx = tid + NT * s;
+      const int k = idx >> 7;
+      A[k * PH + (idx & 127)] = sa[s];
+      Bt[k * PH + tgt_col((idx >> 4) & 7, idx & 15)] = sb[s];
     }
   };
 
@@ -787,16 +743,8 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_bf16_kernel(const uint16_
 // workgroup (both with their r02 epilogues; K loop alone 295 vs 391 us).
 // ---------------------------------------------------------------------------
 constexpr int STAGE_Q2 = 3 * BKH * PH;  // A0, A1, target images (bf16 elements)
-// NHWC (channels-last bf16 fmaps): the three images are
-// stored row-major, one row per query / target (MFMA row order) holding the
-// stage's 32 k, at an 80-byte pitch: a ds_read_b128 hands lane l row l & 31,
-// k 8 (l >> 5) .. +7 — the operand the two transposed reads of the NCHW form
-// assemble — and its 16-lane groups hit 16 distinct 16-byte bank slots
-// (row stride 5 slots).  Same operands, same products: bit-identical pages.
-constexpr int PQN = BKH + 8;             // NHWC row pitch (bf16 elements)
-static_assert(BM * PQN == BKH * PH, "an NHWC image is the size of an NCHW one");
 
-template <typename OT, bool DIV, int MINW, bool NHWC = false>
+template <typename OT, bool DIV, int MINW>
 __global__ __launch_bounds__(2 * NT, MINW) void corr_build_bf16_q2_kernel(
     const uint16_t* __restrict__ f1, const uint16_t* __restrict__ f2, OT* __restrict__ pyr,
     BuildGeom g) {
@@ -807,7 +755,7 @@ __global__ __launch_bounds__(2 * NT, MINW) void corr_build_bf16_q2_kernel(
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int half = wave >> 2, w4 = wave & 3;
-  const PageCoord pc = page_coord<true, 2>(g);
+  const PageCoord pc = banded_coord(g);
   const int th0 = pc.tyi * TH, tw0 = pc.txi * TW;
   const int q0 = pc.qblk * BM;                      // first of the two blocks
   const long long fstride = (long long)g.D * g.N;
@@ -820,84 +768,53 @@ __global__ __launch_bounds__(2 * NT, MINW) void corr_build_bf16_q2_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
-  // NCHW staging units of 4 bf16 (8 B): thread unit s covers idx = tid + 512 s;
+  // Staging units of 4 bf16 (8 B): thread unit s covers idx = tid + 512 s;
   // s = 0,1 -> image A0, 2,3 -> A1, 4,5 -> targets; u = idx & 1023 within the
   // image: k = u >> 5, 4 consecutive queries / target cols.
-  // NHWC units of 8 bf16 (16 B, 8 consecutive k of one pixel): unit s covers
-  // idx = tid + 512 s, image idx >> 9 (A0, A1, targets), u = idx & 511: row
-  // u >> 2, k 8 (u & 3) .. +7.
   // Buffer loads, out-of-range units read zeros.  Host side guarantees
-  // D * N * 2 < 2^31 (and D % 32 == 0 for NHWC).
-  constexpr int NU = NHWC ? 3 : 6;
+  // D * N * 2 < 2^31.
   const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<uint16_t*>(f1b), (short)0, g.D * g.N * 2, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<uint16_t*>(f2b), (short)0, g.D * g.N * 2, 0x00020000);
-  uint32_t vo[NU];
-  int lo[NU];
+  uint32_t vo[6];
+  int lo[6];
 #pragma unroll
-  for (int s = 0; s < NU; ++s) {
-    if constexpr (NHWC) {
-      const int idx = tid + 2 * NT * s, img = idx >> 9, u = idx & 511;
-      const int row = u >> 2, kq = u & 3;
-      if (img < 2) {
-        const int q = q0 + img * BM + row;
-        vo[s] = q < g.N ? (uint32_t)(q * g.D + 8 * kq) * 2u : 0x80000000u;
-        lo[s] = (img * BM + row) * PQN + 8 * kq;
-      } else {
-        const int r = row >> 4, c = row & 15, hh = th0 + r, ww = tw0 + c;
-        vo[s] = (hh < g.H && ww < g.W) ? (uint32_t)((hh * g.W + ww) * g.D + 8 * kq) * 2u
-                                       : 0x80000000u;
-        lo[s] = (2 * BM + tgt_col(r, c)) * PQN + 8 * kq;
-      }
+  for (int s = 0; s < 6; ++s) {
+    const int u = (tid + 2 * NT * s) & 1023, img = s >> 1;
+    const int k = u >> 5;
+    if (img < 2) {
+      const int q = q0 + img * BM + (u & 31) * 4;
+      vo[s] = q < g.N ? (uint32_t)(k * g.N + q) * 2u : 0x80000000u;
+      lo[s] = img * BKH * PH + k * PH + (u & 31) * 4;
     } else {
-      const int u = (tid + 2 * NT * s) & 1023, img = s >> 1;
-      const int k = u >> 5;
-      if (img < 2) {
-        const int q = q0 + img * BM + (u & 31) * 4;
-        vo[s] = q < g.N ? (uint32_t)(k * g.N + q) * 2u : 0x80000000u;
-        lo[s] = img * BKH * PH + k * PH + (u & 31) * 4;
-      } else {
-        const int r = (u >> 2) & 7, c = (u & 3) * 4, hh = th0 + r, ww = tw0 + c;
-        vo[s] = (hh < g.H && ww < g.W) ? (uint32_t)(k * g.N + hh * g.W + ww) * 2u : 0x80000000u;
-        lo[s] = 2 * BKH * PH + k * PH + tgt_col(r, c);
-      }
+      const int r = (u >> 2) & 7, c = (u & 3) * 4, hh = th0 + r, ww = tw0 + c;
+      vo[s] = (hh < g.H && ww < g.W) ? (uint32_t)(k * g.N + hh * g.W + ww) * 2u : 0x80000000u;
+      lo[s] = 2 * BKH * PH + k * PH + tgt_col(r, c);
     }
   }
-  using Unit = std::conditional_t<NHWC, uint4, uint2>;
-  Unit rr[NU];
+  uint2 rr[6];
   auto load = [&](int k0) {
-    const int so = NHWC ? k0 * 2 : k0 * g.N * 2;
+    const int so = k0 * g.N * 2;
 #pragma unroll
-    for (int s = 0; s < NU; ++s) {
-      const __amdgpu_buffer_rsrc_t r = (s < (NHWC ? 2 : 4)) ? rsa : rsb;
-      if constexpr (NHWC)
-        rr[s] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, vo[s], so, 0));
-      else
-        rr[s] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(r, vo[s], so, 0));
+    for (int s = 0; s < 6; ++s) {
+      const __amdgpu_buffer_rsrc_t r = s < 4 ? rsa : rsb;
+      rr[s] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(r, vo[s], so, 0));
     }
   };
   auto store = [&](int buf) {
     uint16_t* S = lh + buf * STAGE_Q2;
 #pragma unroll
-    for (int s = 0; s < NU; ++s) *reinterpret_cast<Unit*>(S + lo[s]) = rr[s];
+    for (int s = 0; s < 6; ++s) *reinterpret_cast<uint2*>(S + lo[s]) = rr[s];
   };
 
   const int li = lane & 15;
-  const int rd_off = NHWC ? (lane & 31) * PQN + 8 * (lane >> 5)
-                          : (li >> 2) * PH + 4 * (li & 3) + 16 * ((lane >> 4) & 1) +
-                                8 * (lane >> 5) * PH;
+  const int rd_off = (li >> 2) * PH + 4 * (li & 3) + 16 * ((lane >> 4) & 1) + 8 * (lane >> 5) * PH;
   auto frag = [&](const uint16_t* p) -> bf8v {
-    if constexpr (NHWC) {
-      return *reinterpret_cast<const bf8v*>(p);
-    } else {
-      return __builtin_bit_cast(bf8v, __builtin_shufflevector(tr_read(p), tr_read(p + 4 * PH), 0,
-                                                              1, 2, 3, 4, 5, 6, 7));
-    }
+    return __builtin_bit_cast(bf8v, __builtin_shufflevector(tr_read(p), tr_read(p + 4 * PH), 0, 1,
+                                                            2, 3, 4, 5, 6, 7));
   };
-  constexpr int KSTEP = NHWC ? 1 : PH;          // LDS elements per k
-  constexpr int RSTEP = NHWC ? 32 * PQN : 32;   // LDS elements per 32 MFMA rows
-  constexpr int IMG = BKH * PH;                 // LDS elements per image (both layouts)
+  constexpr int IMG = BKH * PH;                 // LDS elements per image
   const int nk = (g.D + BKH - 1) / BKH;
   load(0);
   store(0);
@@ -909,10 +826,10 @@ __global__ __launch_bounds__(2 * NT, MINW) void corr_build_bf16_q2_kernel(
     const uint16_t* Bt = lh + buf * STAGE_Q2 + 2 * IMG;
 #pragma unroll
     for (int kk = 0; kk < BKH; kk += 16) {
-      const bf8v qf = frag(A + kk * KSTEP + rd_off + w4 * RSTEP);
+      const bf8v qf = frag(A + kk * PH + rd_off + w4 * 32);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const bf8v tv = frag(Bt + kk * KSTEP + rd_off + t * RSTEP);
+        const bf8v tv = frag(Bt + kk * PH + rd_off + t * 32);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tv, qf, acc[t], 0, 0, 0);
       }
     }
@@ -986,7 +903,7 @@ __device__ __forceinline__ Split3 split3(float a, float b) {
   return {h, m, pack_hi(__float_as_uint(la), __float_as_uint(lb))};
 }
 
-// f16 pair split (H2 form of the split build): x = hi + 2^-11 lo with
+// f16 pair split (main path of the split build): x = hi + 2^-11 lo with
 // hi = RNE_f16(x) and lo = RNE_f16((x - hi) * 2^11).  x - hi is exact in f32 and
 // the scaling is exact, so the representation error is lo's rounding:
 // <= 2^-22 |x| (hi normal) or <= 2^-36 absolute (|x| < 2^-14, lo subnormal).
@@ -1044,9 +961,9 @@ __device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, uint32_t voff
 // loads per lane and the target tile is staged target-major ([target][k] planes,
 // read with ds_read_b128) instead of k-major; same products, same order, same
 // bits as the NCHW build.
-// H2: the f16 pair split (3 products) with the 3-way bf16 split as the
-// per-page overflow fallback; !H2: the 3-way bf16 split only.
-template <typename OT, bool DIV, int MINW, int BV = 4, bool NHWC = false, bool H2 = false>
+// The main path is the f16 pair split (3 products); the 3-way bf16 split is the
+// per-page overflow fallback.
+template <typename OT, bool DIV, int MINW, int BV = 4, bool NHWC = false>
 __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float* __restrict__ f1,
                                                                     const float* __restrict__ f2,
                                                                     OT* __restrict__ pyr,
@@ -1054,12 +971,12 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float*
   constexpr int LDS_E = WAVES * WSTAGE * 4;                         // epilogue bytes
   constexpr int LDS_K = 2 * 3 * (NHWC ? NTGT * 24 : PLANE_S) * 2;     // two stages, bytes
   __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_K > LDS_E ? LDS_K : LDS_E];
-  __shared__ int redo;  // H2: some accumulator of the page is not finite
+  __shared__ int redo;  // some accumulator of the page is not finite
   uint16_t* lh = reinterpret_cast<uint16_t*>(smem);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (H2 && tid == 0) redo = 0;
-  const PageCoord pc = page_coord<false>(g);
+  if (tid == 0) redo = 0;
+  const PageCoord pc = grid_coord(g);
   const int txi = pc.txi, tyi = pc.tyi;
   const int th0 = tyi * TH, tw0 = txi * TW;
   const int q0 = pc.qblk * BM;
@@ -1068,7 +985,7 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float*
   const float* f1b = f1 + b * fstride;
   const float* f2b = f2 + b * fstride;
 
-  f32x16 acc[4], acc2[4];  // acc2: H2 cross terms (hi*lo + lo*hi, scaled 2^11)
+  f32x16 acc[4], acc2[4];  // acc2: pair-split cross terms (hi*lo + lo*hi, scaled 2^11)
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -1139,7 +1056,7 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float*
       }
     }
   };
-  s8v ah, am, al;   // split query operand of the current stage (H2: ah, al)
+  s8v ah, am, al;   // split query operand of the current stage (pair split: ah, al)
   using S3 = std::integral_constant<bool, false>;
   using S2 = std::integral_constant<bool, true>;
   // Operand split by mixed-precision FMAs (split2h_mix: 44 instead of 68 VALU per
@@ -1169,7 +1086,7 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float*
   constexpr int PN = 24;                      // NHWC plane row pitch (bf16)
   constexpr int PLANE_N = NTGT * PN;          // bf16 elements per NHWC plane
   constexpr int PLANE = NHWC ? PLANE_N : PLANE_S;
-  // Target planes of a stage: hi, mid, lo (bf16) or hi, lo (H2: f16).
+  // Target planes of a stage: hi, mid, lo (bf16) or hi, lo (pair split: f16).
   auto store_b = [&](int buf, auto mode) {
     uint16_t* P = lh + buf * 3 * PLANE;
 #pragma unroll
@@ -1259,30 +1176,26 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float*
     }
   };
 
-  if constexpr (H2) {
-    kloop(S2{});
-    // Combine (one rounding) and vote: a non-finite sum means an operand of the
-    // page overflowed f16 (|x| >= 65520) or was itself inf/NaN; the page is then
-    // recomputed on the 3-way bf16 split, which covers the whole f32 range and
-    // propagates inf/NaN operands as the f32 product would.
-    bool bad = false;
+  kloop(S2{});
+  // Combine (one rounding) and vote: a non-finite sum means an operand of the
+  // page overflowed f16 (|x| >= 65520) or was itself inf/NaN; the page is then
+  // recomputed on the 3-way bf16 split, which covers the whole f32 range and
+  // propagates inf/NaN operands as the f32 product would.
+  bool bad = false;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      acc[t][r] = __builtin_fmaf(acc2[t][r], 0x1p-11f, acc[t][r]);
+      bad |= !(__builtin_fabsf(acc[t][r]) <= 3.40282347e38f);
+    }
+  if (bad) redo = 1;
+  __syncthreads();
+  if (redo) {
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        acc[t][r] = __builtin_fmaf(acc2[t][r], 0x1p-11f, acc[t][r]);
-        bad |= !(__builtin_fabsf(acc[t][r]) <= 3.40282347e38f);
-      }
-    if (bad) redo = 1;
-    __syncthreads();
-    if (redo) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-      kloop(S3{});
-    }
-  } else {
+      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
     kloop(S3{});
   }
 
@@ -1347,25 +1260,17 @@ __device__ __forceinline__ int pixel_scale(float m, bool finite) {
 }
 
 // Split 16 consecutive channels of one pixel (already scaled) into the 64-B
-// SP record: hi 16 f16 then lo 16 f16.  LO11: lo = RNE_f16((x - hi) 2^11) (the
-// r02 pair, for experiments), else lo = RNE_f16(x - hi).
-template <bool LO11 = false>
+// SP record: hi 16 f16 then lo 16 f16, lo = RNE_f16(x - hi).
 __device__ __forceinline__ void split_record(const float (&x)[16], uint4 (&rec)[4]) {
   uint32_t h[8], l[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    if constexpr (LO11) {
-      const Split2 p = split2h_mix(x[2 * e], x[2 * e + 1]);
-      h[e] = p.h;
-      l[e] = p.l;
-    } else {
-      h[e] = cvt_pk_f16(x[2 * e], x[2 * e + 1]);
-      const f16x2_t hv = __builtin_bit_cast(f16x2_t, h[e]);
-      f16x2_t lv;
-      lv[0] = (_Float16)__builtin_fmaf((float)hv[0], -1.f, x[2 * e]);
-      lv[1] = (_Float16)__builtin_fmaf((float)hv[1], -1.f, x[2 * e + 1]);
-      l[e] = __builtin_bit_cast(uint32_t, lv);
-    }
+    h[e] = cvt_pk_f16(x[2 * e], x[2 * e + 1]);
+    const f16x2_t hv = __builtin_bit_cast(f16x2_t, h[e]);
+    f16x2_t lv;
+    lv[0] = (_Float16)__builtin_fmaf((float)hv[0], -1.f, x[2 * e]);
+    lv[1] = (_Float16)__builtin_fmaf((float)hv[1], -1.f, x[2 * e + 1]);
+    l[e] = __builtin_bit_cast(uint32_t, lv);
   }
   rec[0] = make_uint4(h[0], h[1], h[2], h[3]);
   rec[1] = make_uint4(h[4], h[5], h[6], h[7]);
@@ -1387,7 +1292,7 @@ __device__ __forceinline__ void split_record(const float (&x)[16], uint4 (&rec)[
 // records stored directly write every line in four partial pieces: 13.7 vs
 // 9.5 us at Sintel B=1 against plain stores, which in turn leave the build's
 // K loop evicting dirty lines.)
-template <bool NHWC, bool LO11 = false, int PX = 64>
+template <bool NHWC, int PX = 64>
 __global__ __launch_bounds__(PX * 16) void split_pairs_kernel(const float* __restrict__ f1,
                                                               const float* __restrict__ f2,
                                                               uint4* __restrict__ sp1,
@@ -1467,7 +1372,7 @@ __global__ __launch_bounds__(PX * 16) void split_pairs_kernel(const float* __res
 #pragma unroll
     for (int i = 0; i < 16; ++i) x[i] = __builtin_ldexpf(x[i], s);
     uint4 rec[4];
-    split_record<LO11>(x, rec);
+    split_record(x, rec);
     // the lane's record -> LDS record u (NCHW: u = pixel; NHWC: u = 4 block + pixel)
     const int u = NHWC ? (lane & 15) * 4 + (lane >> 4) : lane;
 #pragma unroll
@@ -1774,7 +1679,7 @@ __device__ __forceinline__ void dma_quarter(unsigned char* smem, const uint8_t* 
 // p * ps + k * ks of a pair's fmap) on the exact-f32 MFMA, in place: IEEE
 // semantics as the reference's f32 matmul (inf x finite = inf, inf x 0 = NaN,
 // NaN propagates).  Grid: dma_grid(g, B, stream) — [0, g.nmain) whole units in the
-// XCD-banded order (page_coord<true, 2>), then the tail's quarter units.
+// XCD-banded order (banded_coord), then the tail's quarter units.
 //
 // OPK = DMA_BF16 (bf16 mode, C3): the same K loop on bf16 operand records — a
 // 64-B record is 32 consecutive channels of one pixel (k 0-7 | 8-15 | 16-23 |
@@ -1813,7 +1718,7 @@ __global__ __launch_bounds__(2 * NT, 4) void corr_build_dma_kernel(
   // waterfall loop around every buffer_load ... lds
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = wave >> 2, w4 = wave & 3;
-  const PageCoord pc = page_coord<true, 2>(g);
+  const PageCoord pc = banded_coord(g);
   const int th0 = pc.tyi * TH, tw0 = pc.txi * TW;
   const int q0 = pc.qblk * BM;                        // first of the two blocks
   const int b = pc.b;
@@ -2121,9 +2026,8 @@ dim3 build_grid(const BuildGeom& g, int B) {
   return dim3((unsigned)(g.tiles_h * g.tiles_w), (unsigned)((g.N + BM - 1) / BM), (unsigned)B);
 }
 
-// 1-D grid of every page (REMAP launches), or of every group of QB pages along
-// queries.
-dim3 remap_grid(const BuildGeom& g, int B, int QB = 1) {
+// 1-D grid of every group of QB pages along queries (XCD-banded order).
+dim3 remap_grid(const BuildGeom& g, int B, int QB) {
   return dim3((unsigned)((long long)B * ((g.qt + QB - 1) / QB) * g.tiles_h * g.tiles_w));
 }
 
@@ -2136,16 +2040,16 @@ int launch_f32(bool vec, const float* f1, const float* f2, OT* pyr, const BuildG
   const dim3 grid = build_grid(g, B);
   const bool div = g.recip == 0.f;
   if (vec && div)
-    hipLaunchKernelGGL((corr_build_f32_kernel<true, 16, PAGED, OT, 3, true>), grid, dim3(NT), 0,
+    hipLaunchKernelGGL((corr_build_f32_kernel<true, PAGED, OT, 3, true>), grid, dim3(NT), 0,
                        stream, f1, f2, pyr, g);
   else if (vec)
-    hipLaunchKernelGGL((corr_build_f32_kernel<true, 16, PAGED, OT, 3, false>), grid, dim3(NT), 0,
+    hipLaunchKernelGGL((corr_build_f32_kernel<true, PAGED, OT, 3, false>), grid, dim3(NT), 0,
                        stream, f1, f2, pyr, g);
   else if (div)
-    hipLaunchKernelGGL((corr_build_f32_kernel<false, 16, PAGED, OT, 0, true>), grid, dim3(NT), 0,
+    hipLaunchKernelGGL((corr_build_f32_kernel<false, PAGED, OT, 0, true>), grid, dim3(NT), 0,
                        stream, f1, f2, pyr, g);
   else
-    hipLaunchKernelGGL((corr_build_f32_kernel<false, 16, PAGED, OT, 0, false>), grid, dim3(NT), 0,
+    hipLaunchKernelGGL((corr_build_f32_kernel<false, PAGED, OT, 0, false>), grid, dim3(NT), 0,
                        stream, f1, f2, pyr, g);
   return dxr::launch_status();
 }
@@ -2154,21 +2058,6 @@ int launch_f32(bool vec, const float* f1, const float* f2, OT* pyr, const BuildG
 // the 4 workgroups per CU its 40 KB of LDS allows) and the XCD-aware page order
 // (r01 KITTI b8: 721 us vs 837 in grid order).  The scalar-staging path keeps
 // the compiler's choice (it would spill at 3) and the grid order.
-// Channels-last bf16 fmaps: the two-block kernel's NHWC form (D % 32 == 0,
-// 16-byte aligned pixels; checked by the caller).
-template <typename OT>
-int launch_build_bf16_nhwc(const uint16_t* f1, const uint16_t* f2, OT* pyr, const BuildGeom& g,
-                           int B, hipStream_t stream) {
-  const dim3 rg = remap_grid(g, B, 2);
-  if (g.recip == 0.f)
-    hipLaunchKernelGGL((corr_build_bf16_q2_kernel<OT, true, 4, true>), rg, dim3(2 * NT), 0, stream,
-                       f1, f2, pyr, g);
-  else
-    hipLaunchKernelGGL((corr_build_bf16_q2_kernel<OT, false, 4, true>), rg, dim3(2 * NT), 0, stream,
-                       f1, f2, pyr, g);
-  return dxr::launch_status();
-}
-
 template <typename OT>
 int launch_build_bf16(bool vec, const uint16_t* f1, const uint16_t* f2, OT* pyr,
                       const BuildGeom& g, int B, hipStream_t stream) {
@@ -2184,16 +2073,16 @@ int launch_build_bf16(bool vec, const uint16_t* f1, const uint16_t* f2, OT* pyr,
       hipLaunchKernelGGL((corr_build_bf16_q2_kernel<OT, false, 4>), rg, dim3(2 * NT), 0, stream, f1,
                          f2, pyr, g);
   } else if (div) {
-    hipLaunchKernelGGL((corr_build_bf16_kernel<false, OT, true, 0, false>), grid, dim3(NT), 0,
+    hipLaunchKernelGGL((corr_build_bf16_kernel<OT, true, 0>), grid, dim3(NT), 0,
                        stream, f1, f2, pyr, g);
   } else {
-    hipLaunchKernelGGL((corr_build_bf16_kernel<false, OT, false, 0, false>), grid, dim3(NT), 0,
+    hipLaunchKernelGGL((corr_build_bf16_kernel<OT, false, 0>), grid, dim3(NT), 0,
                        stream, f1, f2, pyr, g);
   }
   return dxr::launch_status();
 }
 
-// Split build on the f16 pair split (H2; overflowing pages re-run on the 3-way
+// Split build on the f16 pair split (overflowing pages re-run on the 3-way
 // bf16 split) at 3 waves/SIMD: r02 Sintel 134-142 us against 151-154 for the
 // 3-way bf16 split at 4 waves/SIMD, and 0.4-0.8x its max error against f64
 // (scripts/xp_accuracy.py).
@@ -2202,10 +2091,10 @@ int launch_split(const float* f1, const float* f2, OT* pyr, const BuildGeom& g, 
                  hipStream_t stream) {
   const dim3 grid = build_grid(g, B);
   if (g.recip == 0.f)
-    hipLaunchKernelGGL((corr_build_split_kernel<OT, true, 3, BV, NHWC, true>), grid, dim3(NT),
+    hipLaunchKernelGGL((corr_build_split_kernel<OT, true, 3, BV, NHWC>), grid, dim3(NT),
                        0, stream, f1, f2, pyr, g);
   else
-    hipLaunchKernelGGL((corr_build_split_kernel<OT, false, 3, BV, NHWC, true>), grid, dim3(NT),
+    hipLaunchKernelGGL((corr_build_split_kernel<OT, false, 3, BV, NHWC>), grid, dim3(NT),
                        0, stream, f1, f2, pyr, g);
   return dxr::launch_status();
 }
@@ -2301,7 +2190,7 @@ int launch_dma(const float* f1, const float* f2, OT* pyr, BuildGeom g, int B, vo
   // NCHW: 32 pixels per workgroup, two workgroups per CU (round 4, same-process
   // whole-build A/B: Sintel B=1 115.5 -> 114.4 us, split kernel 13.6 -> 12.4 us)
   constexpr int PX = NHWC ? 64 : 32;
-  hipLaunchKernelGGL((split_pairs_kernel<NHWC, false, PX>),
+  hipLaunchKernelGGL((split_pairs_kernel<NHWC, PX>),
                      dim3((unsigned)((N + PX - 1) / PX), (unsigned)B, 2), dim3(PX * 16), 0, stream,
                      f1, f2, reinterpret_cast<uint4*>(sp1), reinterpret_cast<uint4*>(sp2), e1, e2,
                      g.D, g.N);

@@ -30,45 +30,45 @@ extern "C" int dxr_xp_alt_lookup(const float* fmap1, const float* const* fmap2_l
   for (int l = 0; l < num_levels; ++l)
     g.lv[l] = AltLevel{fmap2_levels[l], L.h[l], L.w[l], 1.f / (float)(1 << l), l * 81};
   if (variant == 0)
-    return launch_alt_mfma_r<4, 1, 0, 1>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 0, 1>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                           stream, ws);
   if (variant == 1)
-    return launch_alt_mfma_r<4, 1, 1>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 1>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                          stream, ws);
   if (variant == 9)   // round 6: one-k-step DMA stages, 4-deep ring per wave
-    return launch_alt_mfma_r<4, 1, 2>(fmap1, coords, out, g, num_levels, (int)B, (int)W, stream, ws);
+    return launch_alt_mfma_r<4, 2>(fmap1, coords, out, g, num_levels, (int)B, (int)W, stream, ws);
   if (variant == 2)
-    return launch_alt_mfma_r<4, 1, 0, 2>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 0, 2>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                              stream, ws);
   if (variant == 3)
-    return launch_alt_mfma_r<4, 1, 0, 4>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 0, 4>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                              stream, ws);
   if (variant == 4)
-    return launch_alt_mfma_r<4, 1, 0, 6>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 0, 6>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                              stream, ws);
   if (variant == 5)
-    return launch_alt_mfma_r<4, 1, 0, 8>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 0, 8>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                              stream, ws);
   if (variant == 11)  // variant 3 without the output stores (timing ablation)
-    return launch_alt_mfma_r<4, 1, 0, 4, 2>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 0, 4, 2>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                                 stream, ws);
   if (variant == 8)   // variant 3 without the cell split (timing ablation)
-    return launch_alt_mfma_r<4, 1, 0, 4, 1>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 0, 4, 1>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                                 stream, ws);
   if (variant == 12)  // variant 3 with every lane loading one of 8 hot cells (ablation: the gather's cost)
-    return launch_alt_mfma_r<4, 1, 0, 4, 4>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 0, 4, 4>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                                 stream, ws);
   if (variant == 13)  // variant 3 without MFMAs (ablation)
-    return launch_alt_mfma_r<4, 1, 0, 4, 8>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 0, 4, 8>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                                 stream, ws);
   if (variant == 14)  // neither cell gathers nor MFMAs nor stores (ablation: the skeleton)
-    return launch_alt_mfma_r<4, 1, 0, 4, 14>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 0, 4, 14>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                                  stream, ws);
   if (variant == 15)  // variant 3 with the round-5 S pitch (100: 4-way phase-2 conflicts)
-    return launch_alt_mfma_r<4, 1, 0, 4, 16>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 0, 4, 16>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                                  stream, ws);
   if (variant == 6 || variant == 7)
-    return launch_alt_mfma_r<4, 1, 0, 4>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
+    return launch_alt_mfma_r<4, 0, 4>(fmap1, coords, out, g, num_levels, (int)B, (int)W,
                                              stream, ws, variant - 6);
   return DXR_EINVAL;
 }

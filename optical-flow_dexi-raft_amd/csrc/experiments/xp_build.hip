@@ -109,7 +109,7 @@ __global__ __launch_bounds__(2 * NT, 4) void xp_build_dma_kernel(
   // waterfall loop around every buffer_load ... lds
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = wave >> 2, w4 = wave & 3;
-  const PageCoord pc = page_coord<true, 2>(g);
+  const PageCoord pc = banded_coord(g);
   const int th0 = pc.tyi * TH, tw0 = pc.txi * TW;
   const int q0 = pc.qblk * BM;                        // first of the two blocks
   const int b = pc.b;
@@ -370,7 +370,7 @@ __global__ __launch_bounds__(PX * 16) void xp_split_px_kernel(const float* __res
 #pragma unroll
   for (int i = 0; i < 16; ++i) x[i] = __builtin_ldexpf(x[i], s);
   uint4 rec[4];
-  split_record<false>(x, rec);
+  split_record(x, rec);
   const unsigned off = (unsigned)((kb0 * N + p) * 64);
 #pragma unroll
   for (int c = 0; c < 4; ++c)   // per-lane 64-B records: partial-line write-through stores
@@ -1219,7 +1219,7 @@ __global__ __launch_bounds__(2 * NT, 4) void xp_dma22_kernel(const uint8_t* __re
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qg = wave & 3, tg = wave >> 2;
-  const PageCoord pc = page_coord<true, 2>(g);
+  const PageCoord pc = banded_coord(g);
   const int th0 = pc.tyi * TH, tw0 = pc.txi * TW;
   const int q0 = pc.qblk * BM;
   const int b = pc.b;
@@ -1413,7 +1413,7 @@ extern "C" int dxr_xp_build22(const float* f1, const float* f2, int64_t B, int64
   uint8_t* sp2 = w + spb;
   int* e1 = reinterpret_cast<int*>(w + 2 * spb);
   int* e2 = reinterpret_cast<int*>(w + 2 * spb + eb);
-  hipLaunchKernelGGL((split_pairs_kernel<false, false, 32>), dim3((unsigned)((N + 31) / 32), (unsigned)B, 2),
+  hipLaunchKernelGGL((split_pairs_kernel<false, 32>), dim3((unsigned)((N + 31) / 32), (unsigned)B, 2),
                      dim3(512), 0, stream, f1, f2, reinterpret_cast<uint4*>(sp1),
                      reinterpret_cast<uint4*>(sp2), e1, e2, g.D, g.N);
   int st = dxr::launch_status();

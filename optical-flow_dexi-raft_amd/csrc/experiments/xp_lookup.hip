@@ -196,6 +196,121 @@ int xp_launch(const PT* pyr, const float* coords, float* out, const LookupGeom& 
   return dxr::launch_status();
 }
 
+// The round 1-5 product: the wide kernel (per-query LDS blocks; the phase 0 and
+// the gathers are corr_lookup.hip's, shared with the lookup backward).
+template <int R, typename PT, int NT_ = 512, int QB_ = 0>
+__global__ __launch_bounds__(NT_) void corr_lookup_wide_kernel(
+    const PT* __restrict__ pyr, const float* __restrict__ coords, float* __restrict__ out,
+    LookupGeom g) {
+  using C = WideCfg<R, NT_, QB_>;
+  constexpr int RD = C::RD, RS = C::RS, K = C::K, QB = C::QB;
+  __shared__ __attribute__((aligned(16))) float cells[QB * C::QS];
+  __shared__ float4 xs[RD * QB];   // {column in the LDS row (int bits), fx, 1-fx, -}
+  __shared__ float4 ys[RD * QB];   // {row offset in LDS (int bits), fy, 1-fy, -}
+  __shared__ int2 org[QB];         // window origin (x, y) or FAR_ORIGIN
+
+  const int tid = threadIdx.x;
+  const int l = blockIdx.y, b = blockIdx.z;
+  const int q0 = blockIdx.x * QB;
+  const LevelAddr A = g.lv[l];
+  // One-dispatch-round grids (the 256 x 16 shape): wave priority by level, finest
+  // first (3 / 2 / 1 / 0), so co-resident level-0 waves, which move the most
+  // lines, issue ahead.  Same-process A/B in the step (r4af): Sintel B=1 203.1 ->
+  // 201.2 us; on multi-round grids (Sintel B=8, KITTI B=8) it cost 0.7-1.5 %.
+  if constexpr (QB_ != 0 && QB_ <= 16) {
+    if (l == 0) __builtin_amdgcn_s_setprio(3);
+    else if (l == 1) __builtin_amdgcn_s_setprio(2);
+    else if (l == 2) __builtin_amdgcn_s_setprio(1);
+  }
+
+  // ---- phase 0
+  wide_phase0<R, NT_, QB_>(coords, g, A, b, l, q0, tid, xs, ys, org);
+  __syncthreads();
+
+  // ---- phase 1 (zeros off the level and for far queries)
+  {
+    const PT* base = pyr + A.off + ((long long)b * A.qt + (q0 >> A.lqb)) * A.qstride;
+    const int qb0 = q0 & ((1 << A.lqb) - 1);
+    // levels 2/3 (tile rows of 4 / 2 cells): query-major slots (round 3: Sintel
+    // B=8 51.5 -> 50.1 us, KITTI B=8 bf16 54.1 -> 51.6 us, bit-identical)
+    if (A.lth == 30)
+      gather_windows<R, NT_, 1, PT, false, QB_>(base, qb0, A, org, cells, q0, g.N, tid);
+    else if (A.tw >= 8)
+      gather_windows<R, NT_, 4, PT, false, QB_>(base, qb0, A, org, cells, q0, g.N, tid);
+    else if (A.tw == 4)
+      gather_windows<R, NT_, 4, PT, true, QB_>(base, qb0, A, org, cells, q0, g.N, tid);
+    else if (A.tw == 2)
+      gather_windows<R, NT_, 2, PT, true, QB_>(base, qb0, A, org, cells, q0, g.N, tid);
+    else
+      gather_windows<R, NT_, 1, PT, false, QB_>(base, qb0, A, org, cells, q0, g.N, tid);
+  }
+  __syncthreads();
+
+  // ---- phase 2
+  const int qq = tid % QB, cls = tid / QB;
+  if (q0 + qq >= g.N) return;
+  const float* cq = cells + qq * C::QS;
+  float* ob = out + ((long long)b * g.cout + (long long)l * K) * g.N + q0 + qq;
+  // output k at ob + k N: a pointer stepped by NCLS N (no per-store multiply)
+  float* op = ob + (long long)cls * g.N;
+  const long long ostep = (long long)C::NCLS * g.N;
+  // (round 4: unrolled and branch-free over the thread's outputs, every LDS read
+  // issued before the first sum, was slower in the step: Sintel B=1 207.3 vs
+  // 204.7 us, Chairs 102.9 vs 100.5, Sintel B=8 1,541 vs 1,519, KITTI B=8 bf16
+  // 1,136 vs 1,107 us)
+  for (int k = cls; k < K; k += C::NCLS) {
+    const int ox = k / RD, oy = k - ox * RD;
+    const float4 xd = xs[ox * QB + qq], yd = ys[oy * QB + qq];
+    const float* p = cq + __float_as_int(yd.x) + __float_as_int(xd.x);
+    const float v00 = p[0], v01 = p[1], v10 = p[RS], v11 = p[RS + 1];
+    const float nw = __fmul_rn(yd.z, xd.z), ne = __fmul_rn(yd.z, xd.y);
+    const float sw = __fmul_rn(yd.y, xd.z), se = __fmul_rn(yd.y, xd.y);
+    float r = __fmul_rn(nw, v00);
+    r = __builtin_fmaf(ne, v01, r);
+    r = __builtin_fmaf(sw, v10, r);
+    r = __builtin_fmaf(se, v11, r);
+    // write-through (sc1) output stores (round 2): the outputs leave the XCD's
+    // L2 while the kernel runs instead of as dirty lines the next kernel
+    // boundary writes back (Sintel B=1 9.5 -> 8.5 us, B=8 58.0 -> 54.6 us).
+    // Round 5: non-temporal stores where a wave's output segments are whole or
+    // aligned half lines (g.out_nt, launch_lookup_r) — they leave the caches
+    // entirely, so the pyramid lines the next lookups gather stay resident.
+    // Round 4: routing them through LDS as 16-byte stores of 4 queries was
+    // slower in the step (Sintel B=1 237.9 vs 222.8 us, B=8 1,623 vs 1,583 us,
+    // KITTI B=8 bf16 1,268 vs 1,193 us).
+    if (g.out_nt) __builtin_nontemporal_store(r, op);
+    else __hip_atomic_store(op, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    op += ostep;
+  }
+}
+
+// Its round-5 launcher: lookup_one_round's shape rule and the out_nt policy of
+// launch_lookup_r (corr_lookup.hip).
+template <int R, typename PT>
+int launch_lookup_wide_r(const PT* pyr, const float* coords, float* out, const LookupGeom& g0, int B,
+                    hipStream_t stream) {
+  using W = WideCfg<R>;
+  LookupGeom g = g0;
+  const long long wg32 = (long long)((g.N + W::QB - 1) / W::QB) * g.levels * B;
+  // pyramid bytes as the build's store rule counts them (dma_stream_out): padded
+  // level-0 pages (qt x 128 queries x whole tiles), x 4/3 for levels 1-3
+  const double pyr_bytes = (double)B * g.lv[0].qt * (double)g.lv[0].qstride * sizeof(PT) * (4.0 / 3.0);
+  const bool big_misaligned = g.N % 32 != 0 && pyr_bytes >= 128.0 * (1 << 20);
+  if (R <= 4 && wg32 <= 1024 && !big_misaligned) {
+    using S = WideCfg<R, 256, 16>;
+    g.out_nt = g.N % 32 == 0 ? 1 : 0;
+    const dim3 grid((unsigned)((g.N + S::QB - 1) / S::QB), (unsigned)g.levels, (unsigned)B);
+    hipLaunchKernelGGL((corr_lookup_wide_kernel<R, PT, 256, 16>), grid, dim3(256), 0, stream, pyr,
+                       coords, out, g);
+    return dxr::launch_status();
+  }
+  g.out_nt = 1;
+  const dim3 grid((unsigned)((g.N + W::QB - 1) / W::QB), (unsigned)g.levels, (unsigned)B);
+  hipLaunchKernelGGL((corr_lookup_wide_kernel<R, PT>), grid, dim3(W::NT), 0, stream, pyr, coords,
+                     out, g);
+  return dxr::launch_status();
+}
+
 // The product kernel with another workgroup shape: NT threads x QB queries
 // (the same 16 threads per query as the product's 512 x 32).
 template <int NT, int QB, typename PT>
