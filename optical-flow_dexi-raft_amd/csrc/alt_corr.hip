@@ -27,11 +27,22 @@
 #include <type_traits>
 
 #include "dxr_common.h"
+#include "mfma_operands.h"
 #include "out_store.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void_t;
+using dxr::f32x16_t;
+using dxr::bf16x8_t;
+using dxr::f16x8_t;
+using dxr::f16x2_t;
+using dxr::cvt_pk_f16;
+using dxr::lds_void_t;
+using dxr::Bf16Split;
+using dxr::Split2;
+using dxr::split2_f16;
+using dxr::split8_f16;
+using dxr::split8_bf16;
 
 struct AltLevel {
   const float* f2;        // [Bf, H2, W2, C]
@@ -202,59 +213,8 @@ __global__ __launch_bounds__(256) void alt_corr_kernel(const float* __restrict__
 // cells are walked in chunks of 4 waves x 32*NRB.  The bilinear combination and
 // the output follow the per-query form exactly.
 // ---------------------------------------------------------------------------
-typedef __bf16 abf8 __attribute__((ext_vector_type(8)));
-typedef float af16 __attribute__((ext_vector_type(16)));
-typedef __bf16 abf2 __attribute__((ext_vector_type(2)));
-typedef float af2 __attribute__((ext_vector_type(2)));
-
 constexpr int TQY = 4, TQX = 8, TQ = TQY * TQX;    // query tile (32 pixels)
 constexpr int ALT_MFMA_C = 256;                    // channels the query planes hold (C <= 256)
-
-__device__ __forceinline__ uint32_t alt_cvt_pk(float a, float b) {
-  const af2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, abf2));
-}
-
-// Exact hi/mid/lo split of 8 floats into three 8 x bf16 operands.
-__device__ __forceinline__ void alt_split8(const float (&x)[8], uint4& h, uint4& m, uint4& l) {
-  uint32_t hh[4], mm[4], ll[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float a = x[2 * e], b = x[2 * e + 1];
-    const uint32_t hp = alt_cvt_pk(a, b);
-    const float ha = __uint_as_float(hp << 16), hb = __uint_as_float(hp & 0xffff0000u);
-    const float ra = __builtin_isinf(ha) ? 0.f : a - ha, rb = __builtin_isinf(hb) ? 0.f : b - hb;
-    const uint32_t mp = alt_cvt_pk(ra, rb);
-    const float la = ra - __uint_as_float(mp << 16), lb = rb - __uint_as_float(mp & 0xffff0000u);
-    hh[e] = hp;
-    mm[e] = mp;
-    ll[e] = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-  }
-  h = make_uint4(hh[0], hh[1], hh[2], hh[3]);
-  m = make_uint4(mm[0], mm[1], mm[2], mm[3]);
-  l = make_uint4(ll[0], ll[1], ll[2], ll[3]);
-}
-
-// f16 pair split of 8 floats (csrc/corr_build.hip split2h): x = hi + 2^-11 lo,
-// hi = RNE_f16(x), lo = RNE_f16((x - hi) * 2^11); valid while |x| < 65520.
-typedef _Float16 ah2 __attribute__((ext_vector_type(2)));
-typedef _Float16 ah8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ uint32_t alt_cvt_pk_h(float a, float b) {
-  const af2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, ah2));
-}
-__device__ __forceinline__ void alt_split8h(const float (&x)[8], uint4& h, uint4& l) {
-  uint32_t hh[4], ll[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float a = x[2 * e], b = x[2 * e + 1];
-    hh[e] = alt_cvt_pk_h(a, b);
-    const ah2 hv = __builtin_bit_cast(ah2, hh[e]);
-    ll[e] = alt_cvt_pk_h((a - (float)hv[0]) * 2048.f, (b - (float)hv[1]) * 2048.f);
-  }
-  h = make_uint4(hh[0], hh[1], hh[2], hh[3]);
-  l = make_uint4(ll[0], ll[1], ll[2], ll[3]);
-}
 
 // The f16 pair split (3 f16 products, cross terms in a second accumulator), as
 // the split build; a chunk whose sums are not finite (an operand beyond f16
@@ -307,7 +267,7 @@ __device__ __forceinline__ void alt_split8h(const float (&x)[8], uint4& h, uint4
 // scaled or recomputed:
 //   - a bfloat16 level: one v_mfma_f32_32x32x16_bf16 per k step on the raw
 //     cell vector and the raw query;
-//   - a float32 level: its cells split three ways by alt_split8 (exact: 3 x 8
+//   - a float32 level: its cells split three ways by split8_bf16<GUARD_INF> (exact: 3 x 8
 //     bits), each part times the raw bfloat16 query — three exact products
 //     (tl q, tm q, th q: small terms first), no query parts; inf and NaN go
 //     through the split as in the float32 form's fallback, so no second pass.
@@ -476,7 +436,7 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
     const float4 c = *reinterpret_cast<const float4*>(src + 4);
     const float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
     uint4 h, l;
-    alt_split8h(x, h, l);
+    split8_f16(x, h, l);
     qplanes[(0 * KB + kb) * TQ + qq] = h;
     qplanes[(1 * KB + kb) * TQ + qq] = l;
   }
@@ -495,7 +455,7 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
   const int j = lane & 31, kh = lane >> 5;
   const int4 qi = qinfo[j];                   // this lane's accumulator column (query j)
   for (int c0 = 0; c0 < ncells; c0 += CHUNK) {
-    af16 acc[NRB];
+    f32x16_t acc[NRB];
     const float* src[NRB];
     const _Float16* srch[NRB];   // IN16, a float16 level
 #pragma unroll
@@ -514,7 +474,7 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
     // (row j, pieces 4 step + 2 kh, + 1) are conflict-free ds_read_b128.  Same operands, same
     // split, same products in the same order: bit-identical to the register form.
     auto kloop_dma = [&]() {
-      af16 acc2 = {};
+      f32x16_t acc2 = {};
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[0][r] = 0.f;
       const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(
@@ -556,12 +516,12 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
           const int p0 = 4 * st + 2 * kh;
           const float4 a = *reinterpret_cast<const float4*>(rb0 + 16 * (p0 ^ sw));
           const float4 b = *reinterpret_cast<const float4*>(rb0 + 16 * ((p0 + 1) ^ sw));
-          const ah8 qh = __builtin_bit_cast(ah8, qplanes[(0 * KB + 2 * ks + kh) * TQ + j]);
-          const ah8 ql = __builtin_bit_cast(ah8, qplanes[(1 * KB + 2 * ks + kh) * TQ + j]);
+          const f16x8_t qh = __builtin_bit_cast(f16x8_t, qplanes[(0 * KB + 2 * ks + kh) * TQ + j]);
+          const f16x8_t ql = __builtin_bit_cast(f16x8_t, qplanes[(1 * KB + 2 * ks + kh) * TQ + j]);
           const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
           uint4 h, l;
-          alt_split8h(x, h, l);
-          const ah8 th = __builtin_bit_cast(ah8, h), tl = __builtin_bit_cast(ah8, l);
+          split8_f16(x, h, l);
+          const f16x8_t th = __builtin_bit_cast(f16x8_t, h), tl = __builtin_bit_cast(f16x8_t, l);
           acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh, acc2, 0, 0, 0);
           acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql, acc2, 0, 0, 0);
           acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, qh, acc[0], 0, 0, 0);
@@ -579,7 +539,7 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
     // ds_read_b128.  Same operands, split and products: bit-identical.
     auto kloop_dma2 = [&]() {
       constexpr int NS = 4;
-      af16 acc2 = {};
+      f32x16_t acc2 = {};
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[0][r] = 0.f;
       const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(
@@ -618,12 +578,12 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
         const unsigned char* rb0 = wreg + (ks % NS) * 2048 + j * 64;
         const float4 a = *reinterpret_cast<const float4*>(rb0 + 16 * ((2 * kh) ^ sw));
         const float4 b = *reinterpret_cast<const float4*>(rb0 + 16 * ((2 * kh + 1) ^ sw));
-        const ah8 qh = __builtin_bit_cast(ah8, qplanes[(0 * KB + 2 * ks + kh) * TQ + j]);
-        const ah8 ql = __builtin_bit_cast(ah8, qplanes[(1 * KB + 2 * ks + kh) * TQ + j]);
+        const f16x8_t qh = __builtin_bit_cast(f16x8_t, qplanes[(0 * KB + 2 * ks + kh) * TQ + j]);
+        const f16x8_t ql = __builtin_bit_cast(f16x8_t, qplanes[(1 * KB + 2 * ks + kh) * TQ + j]);
         const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
         uint4 h, l;
-        alt_split8h(x, h, l);
-        const ah8 th = __builtin_bit_cast(ah8, h), tl = __builtin_bit_cast(ah8, l);
+        split8_f16(x, h, l);
+        const f16x8_t th = __builtin_bit_cast(f16x8_t, h), tl = __builtin_bit_cast(f16x8_t, l);
         acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh, acc2, 0, 0, 0);
         acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql, acc2, 0, 0, 0);
         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, qh, acc[0], 0, 0, 0);
@@ -635,7 +595,7 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
     // cell vectors one k step ahead in registers
     auto kloop = [&](auto h2tag) {
       constexpr bool M2 = decltype(h2tag)::value;
-      af16 acc2[NRB];
+      f32x16_t acc2[NRB];
 #pragma unroll
       for (int rb = 0; rb < NRB; ++rb)
 #pragma unroll
@@ -680,9 +640,9 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
           }
         }
         if constexpr (M2) {
-          const ah8 qh = __builtin_bit_cast(ah8, qplanes[(0 * KB + 2 * ks + kh) * TQ + j]);
+          const f16x8_t qh = __builtin_bit_cast(f16x8_t, qplanes[(0 * KB + 2 * ks + kh) * TQ + j]);
           // (IN16: no low plane — it would be zero — and no th ql product)
-          const ah8 ql = __builtin_bit_cast(ah8, qplanes[((IN16 ? 0 : 1) * KB + 2 * ks + kh) * TQ + j]);
+          const f16x8_t ql = __builtin_bit_cast(f16x8_t, qplanes[((IN16 ? 0 : 1) * KB + 2 * ks + kh) * TQ + j]);
 #pragma unroll
           for (int rb = 0; rb < NRB; ++rb) {
             const float4 a = ca[rb], b = cb[rb];
@@ -692,9 +652,9 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
               l = __builtin_bit_cast(uint4, b);
             } else {
               const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-              alt_split8h(x, h, l);
+              split8_f16(x, h, l);
             }
-            const ah8 th = __builtin_bit_cast(ah8, h), tl = __builtin_bit_cast(ah8, l);
+            const f16x8_t th = __builtin_bit_cast(f16x8_t, h), tl = __builtin_bit_cast(f16x8_t, l);
             if constexpr ((XP & 8) != 0) {   // ablation: no MFMAs (results meaningless)
               acc[rb][0] += __uint_as_float(h.x ^ l.y) + (float)qh[0] + (float)ql[1];
             } else {
@@ -705,36 +665,36 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
             }
           }
         } else {
-          abf8 qh, qm, ql;
+          bf16x8_t qh, qm, ql;
           if constexpr (INBF) {   // the raw bfloat16 query row is the B operand of all three
-            qh = __builtin_bit_cast(abf8, qplanes[(2 * ks + kh) * TQ + j]);
+            qh = __builtin_bit_cast(bf16x8_t, qplanes[(2 * ks + kh) * TQ + j]);
           } else if constexpr (IN16) {   // fallback: the float16 query row, widened here
-            const ah8 u = *reinterpret_cast<const ah8*>(qsrch + ks * 16);
+            const f16x8_t u = *reinterpret_cast<const f16x8_t*>(qsrch + ks * 16);
             const float x[8] = {(float)u[0], (float)u[1], (float)u[2], (float)u[3],
                                 (float)u[4], (float)u[5], (float)u[6], (float)u[7]};
             uint4 h, m, l;
-            alt_split8(x, h, m, l);
-            qh = __builtin_bit_cast(abf8, h);
-            qm = __builtin_bit_cast(abf8, m);
-            ql = __builtin_bit_cast(abf8, l);
+            split8_bf16<Bf16Split::GUARD_INF>(x, h, m, l);
+            qh = __builtin_bit_cast(bf16x8_t, h);
+            qm = __builtin_bit_cast(bf16x8_t, m);
+            ql = __builtin_bit_cast(bf16x8_t, l);
           } else {     // fallback: split the query operand here
             const float4 u = *reinterpret_cast<const float4*>(qsrc + ks * 16);
             const float4 w = *reinterpret_cast<const float4*>(qsrc + ks * 16 + 4);
             const float x[8] = {u.x, u.y, u.z, u.w, w.x, w.y, w.z, w.w};
             uint4 h, m, l;
-            alt_split8(x, h, m, l);
-            qh = __builtin_bit_cast(abf8, h);
-            qm = __builtin_bit_cast(abf8, m);
-            ql = __builtin_bit_cast(abf8, l);
+            split8_bf16<Bf16Split::GUARD_INF>(x, h, m, l);
+            qh = __builtin_bit_cast(bf16x8_t, h);
+            qm = __builtin_bit_cast(bf16x8_t, m);
+            ql = __builtin_bit_cast(bf16x8_t, l);
           }
 #pragma unroll
           for (int rb = 0; rb < NRB; ++rb) {
             const float4 a = ca[rb], b = cb[rb];
             const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
             uint4 h, m, l;
-            alt_split8(x, h, m, l);
-            const abf8 th = __builtin_bit_cast(abf8, h), tm = __builtin_bit_cast(abf8, m),
-                       tl = __builtin_bit_cast(abf8, l);
+            split8_bf16<Bf16Split::GUARD_INF>(x, h, m, l);
+            const bf16x8_t th = __builtin_bit_cast(bf16x8_t, h), tm = __builtin_bit_cast(bf16x8_t, m),
+                       tl = __builtin_bit_cast(bf16x8_t, l);
             if constexpr (INBF) {   // (q has no middle or low part)
               acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tl, qh, acc[rb], 0, 0, 0);
               acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tm, qh, acc[rb], 0, 0, 0);
@@ -788,17 +748,17 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
             rh[u][rb] = *reinterpret_cast<const uint4*>(srch[rb] + (ks + PF) * 16);
         }
         if constexpr (INBF) {
-          const abf8 qb = __builtin_bit_cast(abf8, qplanes[(2 * ks + kh) * TQ + j]);
+          const bf16x8_t qb = __builtin_bit_cast(bf16x8_t, qplanes[(2 * ks + kh) * TQ + j]);
 #pragma unroll
           for (int rb = 0; rb < NRB; ++rb)
-            acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(abf8, ch[rb]), qb,
+            acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, ch[rb]), qb,
                                                               acc[rb], 0, 0, 0);
           continue;
         }
-        const ah8 qh = __builtin_bit_cast(ah8, qplanes[(2 * ks + kh) * TQ + j]);
+        const f16x8_t qh = __builtin_bit_cast(f16x8_t, qplanes[(2 * ks + kh) * TQ + j]);
 #pragma unroll
         for (int rb = 0; rb < NRB; ++rb)
-          acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(ah8, ch[rb]), qh,
+          acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, ch[rb]), qh,
                                                            acc[rb], 0, 0, 0);
       }
     };
@@ -1792,7 +1752,7 @@ namespace {
 // A coarse level's whole volume as one tiled GEMM (round 6): every (query, cell)
 // sum of the level, raw, into that level's pages of the volume buffer — the FULL
 // form's output (and so the on-the-fly lookup's dot products) bit for bit, since
-// each sum is the same three f16 products per k step (alt_split8h operands, cell
+// each sum is the same three f16 products per k step (split8_f16 operands, cell
 // vectors as the A rows, queries as the B columns of v_mfma_f32_32x32x16_f16,
 // cross terms in a second accumulator folded by 2^-11 at the end) in the same k
 // order; only the tiling differs.  The FULL form streams every cell of the level
@@ -1853,7 +1813,7 @@ __global__ __launch_bounds__(256, 2) void alt_volume_gemm_kernel(
     const int q = qblk * 128 + i;
     return q < N ? q * C : -1;
   };
-  af16 acc[2][2], acc2[2][2];
+  f32x16_t acc[2][2], acc2[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -1861,8 +1821,8 @@ __global__ __launch_bounds__(256, 2) void alt_volume_gemm_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][q][r] = acc2[a][q][r] = 0.f;
   // one k step of the wave's 2 x 2 tiles: the windowed form's three products
-  auto mfma_step = [&](const ah8 (&th)[2], const ah8 (&tl)[2], const ah8 (&qh)[2],
-                       const ah8 (&ql)[2]) {
+  auto mfma_step = [&](const f16x8_t (&th)[2], const f16x8_t (&tl)[2], const f16x8_t (&qh)[2],
+                       const f16x8_t (&ql)[2]) {
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -1922,15 +1882,15 @@ __global__ __launch_bounds__(256, 2) void alt_volume_gemm_kernel(
       __syncthreads();
       if (ks + NS - 1 < nks) issue(ks + NS - 1);
       const unsigned char* st = lds + (ks % NS) * SLOT;
-      ah8 th[2], tl[2], qh[2], ql[2];
+      f16x8_t th[2], tl[2], qh[2], ql[2];
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
         const int rc = (wc * 2 + a) * 1024 + j * 32 + kh * 16;
         const int rq = (wq * 2 + a) * 1024 + j * 32 + kh * 16;
-        th[a] = __builtin_bit_cast(ah8, *reinterpret_cast<const uint4*>(st + 0 * 4096 + rc));
-        tl[a] = __builtin_bit_cast(ah8, *reinterpret_cast<const uint4*>(st + 1 * 4096 + rc));
-        qh[a] = __builtin_bit_cast(ah8, *reinterpret_cast<const uint4*>(st + 2 * 4096 + rq));
-        ql[a] = __builtin_bit_cast(ah8, *reinterpret_cast<const uint4*>(st + 3 * 4096 + rq));
+        th[a] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(st + 0 * 4096 + rc));
+        tl[a] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(st + 1 * 4096 + rc));
+        qh[a] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(st + 2 * 4096 + rq));
+        ql[a] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(st + 3 * 4096 + rq));
       }
       mfma_step(th, tl, qh, ql);
     }
@@ -1969,11 +1929,13 @@ __global__ __launch_bounds__(256, 2) void alt_volume_gemm_kernel(
           h0 = __float_as_uint(v.x); h1 = __float_as_uint(v.y);
           l0 = __float_as_uint(v.z); l1 = __float_as_uint(v.w);
         } else {
-          h0 = alt_cvt_pk_h(v.x, v.y);
-          h1 = alt_cvt_pk_h(v.z, v.w);
-          const ah2 a0 = __builtin_bit_cast(ah2, h0), a1 = __builtin_bit_cast(ah2, h1);
-          l0 = alt_cvt_pk_h((v.x - (float)a0[0]) * 2048.f, (v.y - (float)a0[1]) * 2048.f);
-          l1 = alt_cvt_pk_h((v.z - (float)a1[0]) * 2048.f, (v.w - (float)a1[1]) * 2048.f);
+          // split2_f16 of (x, y) and (z, w), both hi words first: through the
+          // pair function this kernel's instructions come out in another order
+          h0 = cvt_pk_f16(v.x, v.y);
+          h1 = cvt_pk_f16(v.z, v.w);
+          const f16x2_t a0 = __builtin_bit_cast(f16x2_t, h0), a1 = __builtin_bit_cast(f16x2_t, h1);
+          l0 = cvt_pk_f16((v.x - (float)a0[0]) * 2048.f, (v.y - (float)a0[1]) * 2048.f);
+          l1 = cvt_pk_f16((v.z - (float)a1[0]) * 2048.f, (v.w - (float)a1[1]) * 2048.f);
         }
         const int a = wr_addr(i);
         *reinterpret_cast<uint2*>(st + a) = make_uint2(h0, h1);
@@ -1989,15 +1951,15 @@ __global__ __launch_bounds__(256, 2) void alt_volume_gemm_kernel(
       const unsigned char* st = lds + (s & 1) * VG_STAGE;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        ah8 th[2], tl[2], qh[2], ql[2];
+        f16x8_t th[2], tl[2], qh[2], ql[2];
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
           const int rc = (wc * 64 + a * 32 + j) * 32 + kh * 16;
           const int rq = (wq * 64 + a * 32 + j) * 32 + kh * 16;
-          th[a] = __builtin_bit_cast(ah8, *reinterpret_cast<const uint4*>(st + (0 + ks) * VG_BLK + rc));
-          tl[a] = __builtin_bit_cast(ah8, *reinterpret_cast<const uint4*>(st + (2 + ks) * VG_BLK + rc));
-          qh[a] = __builtin_bit_cast(ah8, *reinterpret_cast<const uint4*>(st + (4 + ks) * VG_BLK + rq));
-          ql[a] = __builtin_bit_cast(ah8, *reinterpret_cast<const uint4*>(st + (6 + ks) * VG_BLK + rq));
+          th[a] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(st + (0 + ks) * VG_BLK + rc));
+          tl[a] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(st + (2 + ks) * VG_BLK + rc));
+          qh[a] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(st + (4 + ks) * VG_BLK + rq));
+          ql[a] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(st + (6 + ks) * VG_BLK + rq));
         }
         mfma_step(th, tl, qh, ql);
       }
@@ -2018,7 +1980,7 @@ __global__ __launch_bounds__(256, 2) void alt_volume_gemm_kernel(
       }
       if ((XA & 6) == 0 && __ballot(bad) != 0) {   // wave-uniform: the tile on the 3-way bf16 split
         const int co = cell_off(wc * 64 + a * 32 + j), qo = query_off(wq * 64 + q * 32 + j);
-        af16 f = {};
+        f32x16_t f = {};
         for (int ks = 0; ks < C / 16; ++ks) {
           float x[8], y[8];
 #pragma unroll
@@ -2027,12 +1989,12 @@ __global__ __launch_bounds__(256, 2) void alt_volume_gemm_kernel(
             y[e] = qo >= 0 ? f1b[qo + 16 * ks + 8 * kh + e] : 0.f;
           }
           uint4 h, m, l, uh, um, ul;
-          alt_split8(x, h, m, l);
-          alt_split8(y, uh, um, ul);
-          const abf8 th = __builtin_bit_cast(abf8, h), tm = __builtin_bit_cast(abf8, m),
-                     tl = __builtin_bit_cast(abf8, l);
-          const abf8 qh = __builtin_bit_cast(abf8, uh), qm = __builtin_bit_cast(abf8, um),
-                     ql = __builtin_bit_cast(abf8, ul);
+          split8_bf16<Bf16Split::GUARD_INF>(x, h, m, l);
+          split8_bf16<Bf16Split::GUARD_INF>(y, uh, um, ul);
+          const bf16x8_t th = __builtin_bit_cast(bf16x8_t, h), tm = __builtin_bit_cast(bf16x8_t, m),
+                     tl = __builtin_bit_cast(bf16x8_t, l);
+          const bf16x8_t qh = __builtin_bit_cast(bf16x8_t, uh), qm = __builtin_bit_cast(bf16x8_t, um),
+                     ql = __builtin_bit_cast(bf16x8_t, ul);
           f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tm, qm, f, 0, 0, 0);
           f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tl, qh, f, 0, 0, 0);
           f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(th, ql, f, 0, 0, 0);
@@ -2088,7 +2050,7 @@ __global__ __launch_bounds__(256, 2) void alt_volume_gemm_kernel(
 
 // f16 pair planes of `rows` f32 rows of C channels per pair, k-step-major so one
 // k step (16 channels) of consecutive rows is contiguous: out[pair][plane][ks][row][16]
-// with plane 0 = RNE_f16(x), plane 1 = RNE_f16((x - hi) * 2^11) — alt_split8h per
+// with plane 0 = RNE_f16(x), plane 1 = RNE_f16((x - hi) * 2^11) — split8_f16 per
 // element, so the DMA form's products are the register form's.  Thread = 4
 // channels of a row, row-major (a wave reads 1 KB contiguous; its 8-B writes form
 // 32-B runs whose neighbours — the next rows' — the next waves write).
@@ -2103,13 +2065,10 @@ __global__ __launch_bounds__(256) void alt_split_planes_kernel(const float* __re
     const int c = (int)(t - prow * c4n) * 4;
     const long long pair = prow / rows, row = prow - pair * rows;
     const float4 v = *reinterpret_cast<const float4*>(in + 4 * t);
-    const uint32_t h0 = alt_cvt_pk_h(v.x, v.y), h1 = alt_cvt_pk_h(v.z, v.w);
-    const ah2 a0 = __builtin_bit_cast(ah2, h0), a1 = __builtin_bit_cast(ah2, h1);
-    const uint32_t l0 = alt_cvt_pk_h((v.x - (float)a0[0]) * 2048.f, (v.y - (float)a0[1]) * 2048.f);
-    const uint32_t l1 = alt_cvt_pk_h((v.z - (float)a1[0]) * 2048.f, (v.w - (float)a1[1]) * 2048.f);
+    const Split2 s0 = split2_f16(v.x, v.y), s1 = split2_f16(v.z, v.w);
     _Float16* o = out + pair * 2 * rows * C + ((long long)(c >> 4) * rows + row) * 16 + (c & 15);
-    *reinterpret_cast<uint2*>(o) = make_uint2(h0, h1);
-    *reinterpret_cast<uint2*>(o + rows * C) = make_uint2(l0, l1);
+    *reinterpret_cast<uint2*>(o) = make_uint2(s0.h, s1.h);
+    *reinterpret_cast<uint2*>(o + rows * C) = make_uint2(s0.l, s1.l);
   }
 }
 

@@ -34,10 +34,12 @@
 #include <cstdint>
 
 #include "dxr_common.h"
+#include "mfma_operands.h"
 
 namespace {
 
-typedef float bwd_f16v __attribute__((ext_vector_type(16)));
+using dxr::f32x16_t;
+
 
 constexpr int BQY = 4, BQX = 8, BQ = BQY * BQX;   // query tile (32 pixels)
 constexpr int BCH = 32;                           // box cells per chunk
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(256) void alt_corr_bwd_mfma_kernel(
   const float2 qd = qfrac[bq];
   const float* gq = Gs + bq * RR;
 
-  bwd_f16v acc2[BNS];
+  f32x16_t acc2[BNS];
 #pragma unroll
   for (int s = 0; s < BNS; ++s)
 #pragma unroll
@@ -201,7 +203,7 @@ __global__ __launch_bounds__(256) void alt_corr_bwd_mfma_kernel(
         const int c = cb * 32 + j;
         const bool cok = c < C;
         const int cc = cok ? c : 0;
-        bwd_f16v acc1;
+        f32x16_t acc1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc1[r] = 0.f;
 #pragma unroll

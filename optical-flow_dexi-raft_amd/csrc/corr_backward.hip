@@ -18,7 +18,7 @@
 // half a k-block per stage, into the dV operand: folded, split three ways into
 // bf16 (hi, mid, lo) MFMA B-operand records in LDS, one stage ahead of eight
 // MFMA waves that run v_mfma_f32_32x32x16_bf16 with six products (the f32-class
-// split of dxr_common.h split8) against the fmap operand, which comes pre-split
+// split of mfma_operands.h split8_bf16) against the fmap operand, which comes pre-split
 // from a pack pass, one 1 KiB-contiguous record block per wave and k-step.
 // Chunks of k-blocks (split K, so ~256 workgroups fill the chip) write partial
 // sums that a last pass adds in a fixed order: deterministic.
@@ -39,11 +39,17 @@
 #include <type_traits>
 
 #include "dxr_common.h"
+#include "mfma_operands.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
+using dxr::f32x16_t;
+using dxr::bf16x8_t;
+using dxr::f16x8_t;
+using dxr::Bf16Split;
+using dxr::split8_bf16;
+using dxr::split8_f16_prescaled;
+
 
 constexpr int PQ = dxr::PAGE_Q;           // queries per page
 constexpr int TH = dxr::PAGE_H;           // level-0 tile rows
@@ -168,25 +174,6 @@ __device__ __forceinline__ float comp(const uint4& v, int e) {
   return u2f(e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w);
 }
 
-// f16 pair of 8 values scaled by 2^e (|x 2^e| < 2^14 by the choice of e).
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split8h(const float (&v)[8], int e, uint4& hi, uint4& lo) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = __builtin_ldexpf(v[2 * i], e), b = __builtin_ldexpf(v[2 * i + 1], e);
-    const f2v ab = {a, b};
-    const h2v hv = __builtin_convertvector(ab, h2v);
-    const f2v r = {__builtin_fmaf((float)hv[0], -1.f, a), __builtin_fmaf((float)hv[1], -1.f, b)};
-    h[i] = __builtin_bit_cast(uint32_t, hv);
-    l[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, h2v));
-  }
-  hi = make_uint4(h[0], h[1], h[2], h[3]);
-  lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
 // The 8 fmap values of operand record (k-step s, half h) of channel row `src`
 // (one channel's plane of a pair): TORD, k = target in tile order; else k = query.
 template <bool TORD>
@@ -231,7 +218,7 @@ __device__ __forceinline__ bool interior(const GradGeom& g, int qb, int tile) {
 
 __device__ __forceinline__ void store_split(const float (&v)[8], int rec, uint4* __restrict__ sb) {
   uint4 hi, mi, lo;
-  dxr::split8(v, hi, mi, lo);
+  split8_bf16<Bf16Split::GUARD_INF_AND_RANGE>(v, hi, mi, lo);
   sb[rec] = hi;
   sb[REC + rec] = mi;
   sb[2 * REC + rec] = lo;
@@ -250,7 +237,7 @@ __device__ __forceinline__ void store_rec(const float (&v)[8], int rec, uint4* _
                                           int ev) {
   if constexpr (F16) {
     uint4 hi, lo;
-    split8h(v, ev, hi, lo);
+    split8_f16_prescaled(v, ev, hi, lo);
     sb[rec] = hi;
     sb[REC + rec] = lo;
   } else {
@@ -402,7 +389,7 @@ __global__ __launch_bounds__(NTHR) void fmap_grad_kernel(const float* __restrict
 
   const int d0 = slab * DS + wave * 32;
   const bool active = d0 < g.D;  // D % 32 == 0: whole waves
-  f32x16 acc[4];
+  f32x16_t acc[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -433,15 +420,15 @@ __global__ __launch_bounds__(NTHR) void fmap_grad_kernel(const float* __restrict
     const uint4* sp = sb[st & 1] + bl;
 #pragma unroll
     for (int s = 0; s < HK; ++s) {
-      const bf8v qh = __builtin_bit_cast(bf8v, A[s][0]), qm = __builtin_bit_cast(bf8v, A[s][1]),
-                 ql = __builtin_bit_cast(bf8v, A[s][2]);
-      bf8v th[4], tm[4], tl[4];
+      const bf16x8_t qh = __builtin_bit_cast(bf16x8_t, A[s][0]), qm = __builtin_bit_cast(bf16x8_t, A[s][1]),
+                 ql = __builtin_bit_cast(bf16x8_t, A[s][2]);
+      bf16x8_t th[4], tm[4], tl[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const uint4* bp = sp + s * 2 * NB + 32 * j;
-        th[j] = __builtin_bit_cast(bf8v, bp[0]);
-        tm[j] = __builtin_bit_cast(bf8v, bp[REC]);
-        tl[j] = __builtin_bit_cast(bf8v, bp[2 * REC]);
+        th[j] = __builtin_bit_cast(bf16x8_t, bp[0]);
+        tm[j] = __builtin_bit_cast(bf16x8_t, bp[REC]);
+        tl[j] = __builtin_bit_cast(bf16x8_t, bp[2 * REC]);
       }
       // per accumulator small terms first; the four tiles interleaved so no
       // MFMA waits on the one before it
@@ -550,7 +537,7 @@ __device__ __forceinline__ void grad_body(const float* __restrict__ gp, const ui
 
   const int d0 = slab * DS + wave * 32;
   const bool active = d0 < g.D;
-  f32x16 acc[4];
+  f32x16_t acc[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -572,7 +559,7 @@ __device__ __forceinline__ void grad_body(const float* __restrict__ gp, const ui
     } else {
       float x[8];
       load_fmap8<KT>(plane, g, (long long)kb0 * KSTEPS + st * HK + s, hl, x);
-      dxr::split8(x, a[0], a[1], a[NP - 1]);
+      split8_bf16<Bf16Split::GUARD_INF_AND_RANGE>(x, a[0], a[1], a[NP - 1]);
     }
   };
   if (active && nst > 0) {
@@ -586,13 +573,13 @@ __device__ __forceinline__ void grad_body(const float* __restrict__ gp, const ui
 #pragma unroll
     for (int s = 0; s < HK; ++s) {
       if constexpr (F16) {
-        const h8v ah = __builtin_bit_cast(h8v, A[s][0]), al = __builtin_bit_cast(h8v, A[s][1]);
-        h8v th[4], tl[4];
+        const f16x8_t ah = __builtin_bit_cast(f16x8_t, A[s][0]), al = __builtin_bit_cast(f16x8_t, A[s][1]);
+        f16x8_t th[4], tl[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const uint4* bp = sp + s * 2 * NB + 32 * j;
-          th[j] = __builtin_bit_cast(h8v, bp[0]);
-          tl[j] = __builtin_bit_cast(h8v, bp[REC]);
+          th[j] = __builtin_bit_cast(f16x8_t, bp[0]);
+          tl[j] = __builtin_bit_cast(f16x8_t, bp[REC]);
         }
         // small terms first, the four tiles interleaved
 #pragma unroll
@@ -602,15 +589,15 @@ __device__ __forceinline__ void grad_body(const float* __restrict__ gp, const ui
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, th[j], acc[j], 0, 0, 0);
       } else {
-        const bf8v qh = __builtin_bit_cast(bf8v, A[s][0]), qm = __builtin_bit_cast(bf8v, A[s][1]),
-                   ql = __builtin_bit_cast(bf8v, A[s][NP - 1]);
-        bf8v th[4], tm[4], tl[4];
+        const bf16x8_t qh = __builtin_bit_cast(bf16x8_t, A[s][0]), qm = __builtin_bit_cast(bf16x8_t, A[s][1]),
+                   ql = __builtin_bit_cast(bf16x8_t, A[s][NP - 1]);
+        bf16x8_t th[4], tm[4], tl[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const uint4* bp = sp + s * 2 * NB + 32 * j;
-          th[j] = __builtin_bit_cast(bf8v, bp[0]);
-          tm[j] = __builtin_bit_cast(bf8v, bp[REC]);
-          tl[j] = __builtin_bit_cast(bf8v, bp[2 * REC]);
+          th[j] = __builtin_bit_cast(bf16x8_t, bp[0]);
+          tm[j] = __builtin_bit_cast(bf16x8_t, bp[REC]);
+          tl[j] = __builtin_bit_cast(bf16x8_t, bp[2 * REC]);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qm, tm[j], acc[j], 0, 0, 0);
@@ -794,7 +781,7 @@ __global__ __launch_bounds__(1024) void fmap_split16_kernel(const float* __restr
     float x[8];
     load_fmap8<TORD>(f + ((long long)b * g.D + d) * g.N, g, s, h, x);
     uint4 hi, lo;
-    split8h(x, se[dd], hi, lo);
+    split8_f16_prescaled(x, se[dd], hi, lo);
     const long long rec = (((long long)b * 2 * g.ks + s) * g.D + d) * 2 + h;
     fp[rec] = hi;
     fp[rec + pstride] = lo;
@@ -828,7 +815,7 @@ __global__ __launch_bounds__(256) void fmap_split_kernel(const float* __restrict
       for (int e = 0; e < 8; ++e) x[e] = q + e < g.N ? src[q + e] : 0.f;
     }
     uint4 hi, mi, lo;
-    dxr::split8(x, hi, mi, lo);
+    split8_bf16<Bf16Split::GUARD_INF_AND_RANGE>(x, hi, mi, lo);
     const long long rec = (((long long)b * 3 * g.ks + s) * g.D + d) * 2 + h;
     const long long ps = g.ks * g.D * 2;
     fp[rec] = hi;

@@ -30,8 +30,28 @@
 
 #include "build_plan.h"
 #include "dxr_common.h"
+#include "mfma_operands.h"
 
 namespace {
+
+using dxr::f32x16_t;
+using dxr::f32x4_t;
+using dxr::f32x2_t;
+using dxr::bf16x8_t;
+using dxr::f16x8_t;
+using dxr::f16x2_t;
+using dxr::s16x8_t;
+using dxr::s16x4_t;
+using dxr::u32x4_t;
+using dxr::u32x2_t;
+using dxr::lds_void_t;
+using dxr::Bf16Split;
+using dxr::PairLo;
+using dxr::Split2;
+using dxr::Split3;
+using dxr::split2_f16_fused;
+using dxr::split16_f16_record;
+using dxr::split3_bf16;
 
 constexpr int TH = dxr::PAGE_H;  // target tile rows   (image-2 rows)
 constexpr int TW = dxr::PAGE_W;  // target tile cols
@@ -62,7 +82,6 @@ constexpr int WSTAGE = 32 * PQ0; // floats of a wave's private staging region
 static_assert(32 * P1 <= WSTAGE, "the level-1 block fits the staging region");
 static_assert(BM == dxr::PAGE_Q, "one workgroup = one page");
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct BuildGeom {
   int D, H, W, N;       // N = H * W
@@ -254,13 +273,9 @@ __device__ __forceinline__ OT to_out(float v) {
 template <typename OT>
 __device__ __forceinline__ uint32_t to_out2(float a, float b) {
   static_assert(sizeof(OT) == 2, "packed pairs are 16-bit types");
-  if constexpr (std::is_same_v<OT, _Float16>) return dxr::cvt_pk_f16_rne(a, b);
+  if constexpr (std::is_same_v<OT, _Float16>) return dxr::cvt_pk_f16_pinned(a, b);
   else return dxr::cvt_pk_bf16(a, b);
 }
-
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 // Paged epilogue (levels 0..3 of one page), shared by the f32 and bf16 builds.
 // acc holds this wave's 32 queries x 8x16 targets, already divided by sqrt(D).
@@ -305,9 +320,9 @@ __device__ __forceinline__ void epi_put(T* ub, T* p, const V v) {
         __builtin_amdgcn_make_buffer_rsrc(ub, (short)0, 0x7fffffff, 0x00020000);
     const unsigned off = (unsigned)((p - ub) * (long long)sizeof(T));
     if constexpr (sizeof(V) == 16)
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), r, off, 0, AUX);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), r, off, 0, AUX);
     else if constexpr (sizeof(V) == 8)
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, v), r, off, 0, AUX);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, v), r, off, 0, AUX);
     else if constexpr (sizeof(V) == 4)
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, off, 0, AUX);
     else
@@ -324,20 +339,20 @@ template <typename OT, int EX = 0>
 __device__ __forceinline__ void store8(OT* ub, OT* dst, const float* src) {
   const float4 a = f4(src), c = f4(src + 4);
   if constexpr (sizeof(OT) == 2) {
-    u32x4v u;
+    u32x4_t u;
     u.x = to_out2<OT>(a.x, a.y);
     u.y = to_out2<OT>(a.z, a.w);
     u.z = to_out2<OT>(c.x, c.y);
     u.w = to_out2<OT>(c.z, c.w);
     epi_put<EX>(ub, dst, u);
   } else {
-    epi_put<EX>(ub, dst, f32x4v{a.x, a.y, a.z, a.w});
-    epi_put<EX>(ub, dst + 4, f32x4v{c.x, c.y, c.z, c.w});
+    epi_put<EX>(ub, dst, f32x4_t{a.x, a.y, a.z, a.w});
+    epi_put<EX>(ub, dst + 4, f32x4_t{c.x, c.y, c.z, c.w});
   }
 }
 
 template <typename OT, int EX = 0>
-__device__ __forceinline__ float paged_epilogue(f32x16 (&acc)[4], float* lds, OT* __restrict__ pyr,
+__device__ __forceinline__ float paged_epilogue(f32x16_t (&acc)[4], float* lds, OT* __restrict__ pyr,
                                                 const BuildGeom& g, long long page, int wave,
                                                 int lane) {
   const int j = lane & 31, h = lane >> 5;
@@ -365,7 +380,7 @@ __device__ __forceinline__ float paged_epilogue(f32x16 (&acc)[4], float* lds, OT
         const int qq = 2 * k + (lane >> 5) + 16 * ((lane >> 4) & 1);
         const int off = (lane & 15) * 4;
         { const float4 x = f4(wl + qq * PQ0 + off);
-          epi_put<EX>(pb0, pg0 + qq * NTGT + r * (4 * TW) + off, f32x4v{x.x, x.y, x.z, x.w}); }
+          epi_put<EX>(pb0, pg0 + qq * NTGT + r * (4 * TW) + off, f32x4_t{x.x, x.y, x.z, x.w}); }
       }
     } else {
 #pragma unroll
@@ -421,7 +436,7 @@ __device__ __forceinline__ float paged_epilogue(f32x16 (&acc)[4], float* lds, OT
         const int qq = 8 * k + (lane >> 3);
         const int off = (lane & 7) * 4;
         { const float4 x = f4(wl + qq * P1 + off);
-        epi_put<EX>(pb1, pg1 + qq * 32 + off, f32x4v{x.x, x.y, x.z, x.w}); }
+        epi_put<EX>(pb1, pg1 + qq * 32 + off, f32x4_t{x.x, x.y, x.z, x.w}); }
       }
     } else {
 #pragma unroll
@@ -452,9 +467,9 @@ __device__ __forceinline__ float paged_epilogue(f32x16 (&acc)[4], float* lds, OT
       r[2 + i] = __uint_as_float(p[1]);
     }
     if constexpr (sizeof(OT) == 4) {
-      epi_put<EX>(pb2, pg2, f32x4v{r[0], r[1], r[2], r[3]});
+      epi_put<EX>(pb2, pg2, f32x4_t{r[0], r[1], r[2], r[3]});
     } else {
-      u32x2v w;
+      u32x2_t w;
       w.x = to_out2<OT>(r[0], r[1]);
       w.y = to_out2<OT>(r[2], r[3]);
       epi_put<EX>(pb2, pg2, w);
@@ -485,7 +500,7 @@ constexpr int build_lds_floats() {
 // DIV = true performs the IEEE division (compiled only where it is needed, as
 // its expansion costs registers).
 template <bool DIV>
-__device__ __forceinline__ void scale_acc(f32x16 (&acc)[4], const BuildGeom& g) {
+__device__ __forceinline__ void scale_acc(f32x16_t (&acc)[4], const BuildGeom& g) {
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -525,7 +540,7 @@ __device__ __forceinline__ void build_page_f32(const float* __restrict__ f1,
   const int qry_off = wave * 32 + j;
   const int khalf = lane >> 5;
 
-  f32x16 acc[4];
+  f32x16_t acc[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -616,18 +631,15 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_f32_kernel(const float* _
 // reads conflict-free (rows 16 banks apart, the two 16-lane groups of a half 8
 // banks apart).
 // ---------------------------------------------------------------------------
-typedef short s4v __attribute__((ext_vector_type(4)));
-typedef short s8v __attribute__((ext_vector_type(8)));
-typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
 
 constexpr int BKH = 32;            // K per stage (two 16-deep MFMA steps)
 constexpr int PH = BM + 32;        // LDS row pitch in bf16 elements (320 B)
 static_assert(NTGT + 32 == PH, "A and B images share the pitch");
 constexpr int STAGE_H = 2 * BKH * PH;  // bf16 elements per stage (A image + B image)
 
-__device__ __forceinline__ s4v tr_read(const uint16_t* p) {
+__device__ __forceinline__ s16x4_t tr_read(const uint16_t* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s4v*)(p));
+      (__attribute__((address_space(3))) s16x4_t*)(p));
 }
 
 // LDS column of target (tile row r in 0..7, tile col c in 0..15): MFMA tile
@@ -655,7 +667,7 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_bf16_kernel(const uint16_
   const uint16_t* f1b = f1 + b * fstride;
   const uint16_t* f2b = f2 + b * fstride;
 
-  f32x16 acc[4];
+  f32x16_t acc[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -710,15 +722,15 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_bf16_kernel(const uint16_
 #pragma unroll
     for (int kk = 0; kk < BKH; kk += 16) {
       const uint16_t* pa = A + kk * PH + rd_off + wave * 32;
-      const s8v qv = __builtin_shufflevector(tr_read(pa), tr_read(pa + 4 * PH), 0, 1, 2, 3, 4, 5,
+      const s16x8_t qv = __builtin_shufflevector(tr_read(pa), tr_read(pa + 4 * PH), 0, 1, 2, 3, 4, 5,
                                              6, 7);
-      const bf8v qf = __builtin_bit_cast(bf8v, qv);
+      const bf16x8_t qf = __builtin_bit_cast(bf16x8_t, qv);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const uint16_t* pb = Bt + kk * PH + rd_off + t * 32;
-        const s8v tv = __builtin_shufflevector(tr_read(pb), tr_read(pb + 4 * PH), 0, 1, 2, 3, 4,
+        const s16x8_t tv = __builtin_shufflevector(tr_read(pb), tr_read(pb + 4 * PH), 0, 1, 2, 3, 4,
                                                5, 6, 7);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8v, tv), qf, acc[t],
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, tv), qf, acc[t],
                                                          0, 0, 0);
       }
     }
@@ -762,7 +774,7 @@ __global__ __launch_bounds__(2 * NT, MINW) void corr_build_bf16_q2_kernel(
   const uint16_t* f1b = f1 + pc.b * fstride;
   const uint16_t* f2b = f2 + pc.b * fstride;
 
-  f32x16 acc[4];
+  f32x16_t acc[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -810,8 +822,8 @@ __global__ __launch_bounds__(2 * NT, MINW) void corr_build_bf16_q2_kernel(
 
   const int li = lane & 15;
   const int rd_off = (li >> 2) * PH + 4 * (li & 3) + 16 * ((lane >> 4) & 1) + 8 * (lane >> 5) * PH;
-  auto frag = [&](const uint16_t* p) -> bf8v {
-    return __builtin_bit_cast(bf8v, __builtin_shufflevector(tr_read(p), tr_read(p + 4 * PH), 0, 1,
+  auto frag = [&](const uint16_t* p) -> bf16x8_t {
+    return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(tr_read(p), tr_read(p + 4 * PH), 0, 1,
                                                             2, 3, 4, 5, 6, 7));
   };
   constexpr int IMG = BKH * PH;                 // LDS elements per image
@@ -826,10 +838,10 @@ __global__ __launch_bounds__(2 * NT, MINW) void corr_build_bf16_q2_kernel(
     const uint16_t* Bt = lh + buf * STAGE_Q2 + 2 * IMG;
 #pragma unroll
     for (int kk = 0; kk < BKH; kk += 16) {
-      const bf8v qf = frag(A + kk * PH + rd_off + w4 * 32);
+      const bf16x8_t qf = frag(A + kk * PH + rd_off + w4 * 32);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const bf8v tv = frag(Bt + kk * PH + rd_off + t * 32);
+        const bf16x8_t tv = frag(Bt + kk * PH + rd_off + t * 32);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tv, qf, acc[t], 0, 0, 0);
       }
     }
@@ -874,67 +886,10 @@ __global__ __launch_bounds__(2 * NT, MINW) void corr_build_bf16_q2_kernel(
 constexpr int BKS = 16;                 // K per stage
 constexpr int PLANE_S = BKS * PH;       // bf16 elements per split plane
 
-struct Split3 {
-  uint32_t h, m, l;  // bf16x2 words (first element in the low half)
-};
-
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-
-// v_cvt_pk_bf16_f32: round-to-nearest-even of two floats into one bf16x2 word.
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
-  const f32x2_t v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-
-// bf16x2 word of the high halves of two f32 bit patterns (element a low).
-__device__ __forceinline__ uint32_t pack_hi(uint32_t a, uint32_t b) {
-  return __builtin_amdgcn_perm(b, a, 0x07060302u);
-}
-
-// Exact 3-way split of two floats (see above), packed for the MFMA operands.
-__device__ __forceinline__ Split3 split3(float a, float b) {
-  const uint32_t h = cvt_pk_bf16(a, b);
-  // an infinite hi keeps mid = lo = 0 (inf - inf would make them NaN: x*y must stay +-inf)
-  const float ha = __uint_as_float(h << 16), hb = __uint_as_float(h & 0xffff0000u);
-  const float ra = __builtin_isinf(ha) ? 0.f : a - ha, rb = __builtin_isinf(hb) ? 0.f : b - hb;
-  const uint32_t m = cvt_pk_bf16(ra, rb);
-  const float la = ra - __uint_as_float(m << 16), lb = rb - __uint_as_float(m & 0xffff0000u);
-  return {h, m, pack_hi(__float_as_uint(la), __float_as_uint(lb))};
-}
-
-// f16 pair split (main path of the split build): x = hi + 2^-11 lo with
-// hi = RNE_f16(x) and lo = RNE_f16((x - hi) * 2^11).  x - hi is exact in f32 and
-// the scaling is exact, so the representation error is lo's rounding:
-// <= 2^-22 |x| (hi normal) or <= 2^-36 absolute (|x| < 2^-14, lo subnormal).
-// x*y = hi*hi + 2^-11 (hi*lo + lo*hi) + 2^-22 lo*lo; the last term (<= 2^-22 |x y|,
-// sign-symmetric under RNE) is dropped.  f16 x f16 products are exact in f32.
-// Valid while |x| < 65520 (hi finite): the kernel detects the overflow from its
-// own accumulators and re-runs the page on the 3-way bf16 split.
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-
-struct Split2 {
-  uint32_t h, l;  // f16x2 words (first element in the low half)
-};
-
-__device__ __forceinline__ uint32_t cvt_pk_f16(float a, float b) {
-  const f32x2_t v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_t));
-}
-
-// The residual is formed and rounded by mixed-precision FMAs:
-// lo = RNE_f16(fma(hi, -2048, 2048 x)).  2048 x and 2048 hi are exact and so is
-// their difference (= 2048 (x - hi)), so the single rounding is the RNE of
-// (x - hi) * 2^11; hi stays an f16 operand (v_fma_mix*_f16), no conversion back.
-__device__ __forceinline__ Split2 split2h_mix(float a, float b) {
-  const uint32_t h = cvt_pk_f16(a, b);
-  const f16x2_t hv = __builtin_bit_cast(f16x2_t, h);
-  f16x2_t lv;
-  lv[0] = (_Float16)__builtin_fmaf((float)hv[0], -2048.f, a * 2048.f);
-  lv[1] = (_Float16)__builtin_fmaf((float)hv[1], -2048.f, b * 2048.f);
-  return {h, __builtin_bit_cast(uint32_t, lv)};
-}
+// The splits themselves (split3_bf16<GUARD_INF>, the fallback; the f16 pair by
+// mixed-precision FMAs, split2_f16_fused<SCALED_2_11>, the main path, which
+// detects an operand beyond f16 range from its own accumulators and re-runs the
+// page on the fallback) are mfma_operands.h's.
 
 // Raw buffer access (gfx9 resource word 3: 0x00020000), byte offsets.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, int elems) {
@@ -945,12 +900,11 @@ __device__ __forceinline__ float bload1(__amdgpu_buffer_rsrc_t r, uint32_t voff,
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
 __device__ __forceinline__ float2 bload2(__amdgpu_buffer_rsrc_t r, uint32_t voff, int soff) {
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  const f2 v = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
+  const f32x2_t v = __builtin_bit_cast(f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
   return make_float2(v.x, v.y);
 }
 __device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, uint32_t voff, int soff) {
-  const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
+  const f32x4_t v = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
   return make_float4(v.x, v.y, v.z, v.w);
 }
 
@@ -985,7 +939,7 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float*
   const float* f1b = f1 + b * fstride;
   const float* f2b = f2 + b * fstride;
 
-  f32x16 acc[4], acc2[4];  // acc2: pair-split cross terms (hi*lo + lo*hi, scaled 2^11)
+  f32x16_t acc[4], acc2[4];  // acc2: pair-split cross terms (hi*lo + lo*hi, scaled 2^11)
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -1056,30 +1010,30 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float*
       }
     }
   };
-  s8v ah, am, al;   // split query operand of the current stage (pair split: ah, al)
+  s16x8_t ah, am, al;   // split query operand of the current stage (pair split: ah, al)
   using S3 = std::integral_constant<bool, false>;
   using S2 = std::integral_constant<bool, true>;
-  // Operand split by mixed-precision FMAs (split2h_mix: 44 instead of 68 VALU per
-  // k step, bit-identical to split2h; Sintel step 225.4 -> 223.6 us).
+  // Operand split by mixed-precision FMAs (split2_f16_fused: 44 instead of 68 VALU
+  // per k step, bit-identical to split2_f16; Sintel step 225.4 -> 223.6 us).
   auto split_a = [&](auto mode) {
     uint32_t h[4], m[4], l[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if constexpr (decltype(mode)::value) {
-        const Split2 x = split2h_mix(an[2 * e], an[2 * e + 1]);
+        const Split2 x = split2_f16_fused<PairLo::SCALED_2_11>(an[2 * e], an[2 * e + 1]);
         h[e] = x.h;
         m[e] = 0;
         l[e] = x.l;
       } else {
-        const Split3 x = split3(an[2 * e], an[2 * e + 1]);
+        const Split3 x = split3_bf16<Bf16Split::GUARD_INF>(an[2 * e], an[2 * e + 1]);
         h[e] = x.h;
         m[e] = x.m;
         l[e] = x.l;
       }
     }
-    ah = __builtin_bit_cast(s8v, make_uint4(h[0], h[1], h[2], h[3]));
-    am = __builtin_bit_cast(s8v, make_uint4(m[0], m[1], m[2], m[3]));
-    al = __builtin_bit_cast(s8v, make_uint4(l[0], l[1], l[2], l[3]));
+    ah = __builtin_bit_cast(s16x8_t, make_uint4(h[0], h[1], h[2], h[3]));
+    am = __builtin_bit_cast(s16x8_t, make_uint4(m[0], m[1], m[2], m[3]));
+    al = __builtin_bit_cast(s16x8_t, make_uint4(l[0], l[1], l[2], l[3]));
   };
   // NHWC target planes: [target (MFMA row order)][16 k] bf16 at a 48-byte
   // pitch, which keeps the ds_read_b128 lane groups bank-conflict free.
@@ -1093,9 +1047,9 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float*
     for (int s = 0; s < NBS; ++s) {
       const int o = NHWC ? bcol[s] * PN + bk[s] : bk[s] * PH + bcol[s];
       if constexpr (decltype(mode)::value) {
-        const Split2 x = split2h_mix(bn[s].x, bn[s].y);
+        const Split2 x = split2_f16_fused<PairLo::SCALED_2_11>(bn[s].x, bn[s].y);
         if constexpr (BV == 4) {
-          const Split2 z = split2h_mix(bn[s].z, bn[s].w);
+          const Split2 z = split2_f16_fused<PairLo::SCALED_2_11>(bn[s].z, bn[s].w);
           *reinterpret_cast<uint2*>(P + o) = make_uint2(x.h, z.h);
           *reinterpret_cast<uint2*>(P + PLANE + o) = make_uint2(x.l, z.l);
         } else {
@@ -1103,9 +1057,9 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float*
           *reinterpret_cast<uint32_t*>(P + PLANE + o) = x.l;
         }
       } else {
-        const Split3 x = split3(bn[s].x, bn[s].y);
+        const Split3 x = split3_bf16<Bf16Split::GUARD_INF>(bn[s].x, bn[s].y);
         if constexpr (BV == 4) {
-          const Split3 z = split3(bn[s].z, bn[s].w);
+          const Split3 z = split3_bf16<Bf16Split::GUARD_INF>(bn[s].z, bn[s].w);
           *reinterpret_cast<uint2*>(P + o) = make_uint2(x.h, z.h);
           *reinterpret_cast<uint2*>(P + PLANE + o) = make_uint2(x.m, z.m);
           *reinterpret_cast<uint2*>(P + 2 * PLANE + o) = make_uint2(x.l, z.l);
@@ -1124,9 +1078,9 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float*
                                 8 * (lane >> 5) * PH;
   auto frag = [&](const uint16_t* p) {
     if constexpr (NHWC) {
-      return *reinterpret_cast<const bf8v*>(p);
+      return *reinterpret_cast<const bf16x8_t*>(p);
     } else {
-      return __builtin_bit_cast(bf8v, __builtin_shufflevector(tr_read(p), tr_read(p + 4 * PH), 0,
+      return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(tr_read(p), tr_read(p + 4 * PH), 0,
                                                               1, 2, 3, 4, 5, 6, 7));
     }
   };
@@ -1148,16 +1102,16 @@ __global__ __launch_bounds__(NT, MINW) void corr_build_split_kernel(const float*
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         if constexpr (M2) {
-          const h8v th = __builtin_bit_cast(h8v, frag(P + t * tstride)),
-                    tl = __builtin_bit_cast(h8v, frag(P + PLANE + t * tstride));
-          const h8v qh = __builtin_bit_cast(h8v, ah), ql = __builtin_bit_cast(h8v, al);
+          const f16x8_t th = __builtin_bit_cast(f16x8_t, frag(P + t * tstride)),
+                    tl = __builtin_bit_cast(f16x8_t, frag(P + PLANE + t * tstride));
+          const f16x8_t qh = __builtin_bit_cast(f16x8_t, ah), ql = __builtin_bit_cast(f16x8_t, al);
           acc2[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh, acc2[t], 0, 0, 0);
           acc2[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql, acc2[t], 0, 0, 0);
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, qh, acc[t], 0, 0, 0);
         } else {
-          const bf8v qh = __builtin_bit_cast(bf8v, ah), qm = __builtin_bit_cast(bf8v, am),
-                     ql = __builtin_bit_cast(bf8v, al);
-          const bf8v th = frag(P + t * tstride), tm = frag(P + PLANE + t * tstride),
+          const bf16x8_t qh = __builtin_bit_cast(bf16x8_t, ah), qm = __builtin_bit_cast(bf16x8_t, am),
+                     ql = __builtin_bit_cast(bf16x8_t, al);
+          const bf16x8_t th = frag(P + t * tstride), tm = frag(P + PLANE + t * tstride),
                      tl = frag(P + 2 * PLANE + t * tstride);
           // small terms first
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tm, qm, acc[t], 0, 0, 0);
@@ -1259,25 +1213,6 @@ __device__ __forceinline__ int pixel_scale(float m, bool finite) {
   return s < -125 ? -125 : (s > 125 ? 125 : s);
 }
 
-// Split 16 consecutive channels of one pixel (already scaled) into the 64-B
-// SP record: hi 16 f16 then lo 16 f16, lo = RNE_f16(x - hi).
-__device__ __forceinline__ void split_record(const float (&x)[16], uint4 (&rec)[4]) {
-  uint32_t h[8], l[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    h[e] = cvt_pk_f16(x[2 * e], x[2 * e + 1]);
-    const f16x2_t hv = __builtin_bit_cast(f16x2_t, h[e]);
-    f16x2_t lv;
-    lv[0] = (_Float16)__builtin_fmaf((float)hv[0], -1.f, x[2 * e]);
-    lv[1] = (_Float16)__builtin_fmaf((float)hv[1], -1.f, x[2 * e + 1]);
-    l[e] = __builtin_bit_cast(uint32_t, lv);
-  }
-  rec[0] = make_uint4(h[0], h[1], h[2], h[3]);
-  rec[1] = make_uint4(h[4], h[5], h[6], h[7]);
-  rec[2] = make_uint4(l[0], l[1], l[2], l[3]);
-  rec[3] = make_uint4(l[4], l[5], l[6], l[7]);
-}
-
 // One thread per (pixel, 16-channel block): 1024-thread blocks of 64 pixels x
 // 16 channel blocks (more blocks loop), grid (ceil(N / 64), B, 2 fmaps).  NCHW:
 // wave = channel block, lane = pixel, so every load is 256 contiguous bytes;
@@ -1372,7 +1307,7 @@ __global__ __launch_bounds__(PX * 16) void split_pairs_kernel(const float* __res
 #pragma unroll
     for (int i = 0; i < 16; ++i) x[i] = __builtin_ldexpf(x[i], s);
     uint4 rec[4];
-    split_record(x, rec);
+    split16_f16_record(x, rec);
     // the lane's record -> LDS record u (NCHW: u = pixel; NHWC: u = 4 block + pixel)
     const int u = NHWC ? (lane & 15) * 4 + (lane >> 4) : lane;
 #pragma unroll
@@ -1388,7 +1323,7 @@ __global__ __launch_bounds__(PX * 16) void split_pairs_kernel(const float* __res
       const int px = NHWC ? blockIdx.x * 64 + wave * 4 + (u2 & 3) : blockIdx.x * PX + u2 % PX;
       if (px < N && kbs < nkb) {
         const uint4 v = tw[u2 * 5 + c];
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), rs,
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs,
                                                (unsigned)((kbs * N + px) * 64 + c * 16), 0, 16);
       }
     }
@@ -1398,7 +1333,6 @@ __global__ __launch_bounds__(PX * 16) void split_pairs_kernel(const float* __res
   }
 }
 
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 // Operand kind of the DMA build (corr_build_dma_kernel, dma_quarter): scaled f16
 // pairs of f32 fmaps (split_pairs_kernel), or 64-byte records of 32 consecutive
@@ -1422,7 +1356,7 @@ static_assert(DMA_XS_BYTES + WAVES * WSTAGE * 4 <= DMA_LDS_RING, "tail exchange 
 // the exact-f32 MFMA and write them again.  acc[t][r] is query qj x tile pixel
 // (row 2t + kh, col r).  Shared by the whole-unit and the quarter-unit forms.
 template <typename OT, bool DIV, int EXF = 5>
-__device__ __forceinline__ void dma_finish_f32(f32x16 (&acc)[4], const BuildGeom& g,
+__device__ __forceinline__ void dma_finish_f32(f32x16_t (&acc)[4], const BuildGeom& g,
                                                OT* __restrict__ pyr, float* stage, long long page,
                                                int w4, int lane, int sq, int qj,
                                                int trow0, int th0, int tw0, int b,
@@ -1602,7 +1536,7 @@ __device__ __forceinline__ void dma_quarter(unsigned char* smem, const uint8_t* 
   const int th_off = DMA_TILE + t * 2048 + trow0 * 64 + 16 * (kh ^ kt);
   const int tl_off = DMA_TILE + t * 2048 + trow0 * 64 + 16 * ((2 + kh) ^ kt);
 
-  f32x16 acc;
+  f32x16_t acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1622,24 +1556,24 @@ __device__ __forceinline__ void dma_quarter(unsigned char* smem, const uint8_t* 
     if (kk + 2 < nk) dma(kk + 2);
     const unsigned char* st = smem + (kk % DMA_RING) * DMA_STAGE;
     if constexpr (OPK == DMA_BF16) {
-      const bf8v q0v = *reinterpret_cast<const bf8v*>(st + qh_off);
-      const bf8v q1v = *reinterpret_cast<const bf8v*>(st + ql_off);
-      const bf8v t0v = *reinterpret_cast<const bf8v*>(st + th_off);
-      const bf8v t1v = *reinterpret_cast<const bf8v*>(st + tl_off);
+      const bf16x8_t q0v = *reinterpret_cast<const bf16x8_t*>(st + qh_off);
+      const bf16x8_t q1v = *reinterpret_cast<const bf16x8_t*>(st + ql_off);
+      const bf16x8_t t0v = *reinterpret_cast<const bf16x8_t*>(st + th_off);
+      const bf16x8_t t1v = *reinterpret_cast<const bf16x8_t*>(st + tl_off);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t0v, q0v, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t1v, q1v, acc, 0, 0, 0);
     } else if constexpr (OPK == DMA_F16) {
-      const h8v q0v = *reinterpret_cast<const h8v*>(st + qh_off);
-      const h8v q1v = *reinterpret_cast<const h8v*>(st + ql_off);
-      const h8v t0v = *reinterpret_cast<const h8v*>(st + th_off);
-      const h8v t1v = *reinterpret_cast<const h8v*>(st + tl_off);
+      const f16x8_t q0v = *reinterpret_cast<const f16x8_t*>(st + qh_off);
+      const f16x8_t q1v = *reinterpret_cast<const f16x8_t*>(st + ql_off);
+      const f16x8_t t0v = *reinterpret_cast<const f16x8_t*>(st + th_off);
+      const f16x8_t t1v = *reinterpret_cast<const f16x8_t*>(st + tl_off);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(t0v, q0v, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(t1v, q1v, acc, 0, 0, 0);
     } else {
-      const h8v qh = *reinterpret_cast<const h8v*>(st + qh_off);
-      const h8v ql = *reinterpret_cast<const h8v*>(st + ql_off);
-      const h8v th = *reinterpret_cast<const h8v*>(st + th_off);
-      const h8v tl = *reinterpret_cast<const h8v*>(st + tl_off);
+      const f16x8_t qh = *reinterpret_cast<const f16x8_t*>(st + qh_off);
+      const f16x8_t ql = *reinterpret_cast<const f16x8_t*>(st + ql_off);
+      const f16x8_t th = *reinterpret_cast<const f16x8_t*>(st + th_off);
+      const f16x8_t tl = *reinterpret_cast<const f16x8_t*>(st + tl_off);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, qh, acc, 0, 0, 0);
@@ -1655,7 +1589,7 @@ __device__ __forceinline__ void dma_quarter(unsigned char* smem, const uint8_t* 
         make_float4(acc[4 * u], acc[4 * u + 1], acc[4 * u + 2], acc[4 * u + 3]);
   __syncthreads();
   if (t != 0) return;             // one wave per group writes (wave-local syncs below)
-  f32x16 a4[4];
+  f32x16_t a4[4];
 #pragma unroll
   for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
@@ -1773,7 +1707,7 @@ __global__ __launch_bounds__(2 * NT, 4) void corr_build_dma_kernel(
   const int th_off = DMA_TILE + trow0 * 64 + 16 * (kh ^ kt);
   const int tl_off = DMA_TILE + trow0 * 64 + 16 * ((2 + kh) ^ kt);
 
-  f32x16 acc[4];
+  f32x16_t acc[4];
   // exponent loads and LDS writes above must not count against the ring's vmcnt
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   const int nk = g.D / (BF ? 2 * BKS : BKS);
@@ -1795,43 +1729,43 @@ __global__ __launch_bounds__(2 * NT, 4) void corr_build_dma_kernel(
     const unsigned char* st = smem + (kk % DMA_RING) * DMA_STAGE;
     if constexpr (OPK == DMA_F16) {
       // the bf16 records' stage on the f16 MFMA: k 0-15 for every tile, then k 16-31
-      const h8v q0v = *reinterpret_cast<const h8v*>(st + qh_off);
-      const h8v q1v = *reinterpret_cast<const h8v*>(st + ql_off);
+      const f16x8_t q0v = *reinterpret_cast<const f16x8_t*>(st + qh_off);
+      const f16x8_t q1v = *reinterpret_cast<const f16x8_t*>(st + ql_off);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const h8v t0v = *reinterpret_cast<const h8v*>(st + th_off + t * 2048);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(t0v, q0v, FIRST ? f32x16{} : acc[t], 0, 0,
+        const f16x8_t t0v = *reinterpret_cast<const f16x8_t*>(st + th_off + t * 2048);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(t0v, q0v, FIRST ? f32x16_t{} : acc[t], 0, 0,
                                                         0);
       }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const h8v t1v = *reinterpret_cast<const h8v*>(st + tl_off + t * 2048);
+        const f16x8_t t1v = *reinterpret_cast<const f16x8_t*>(st + tl_off + t * 2048);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(t1v, q1v, acc[t], 0, 0, 0);
       }
     } else if constexpr (OPK == DMA_BF16) {
       // k 0-15 of the stage for every tile, then k 16-31 (the q2 kernel's order)
-      const bf8v q0v = *reinterpret_cast<const bf8v*>(st + qh_off);
-      const bf8v q1v = *reinterpret_cast<const bf8v*>(st + ql_off);
+      const bf16x8_t q0v = *reinterpret_cast<const bf16x8_t*>(st + qh_off);
+      const bf16x8_t q1v = *reinterpret_cast<const bf16x8_t*>(st + ql_off);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const bf8v t0v = *reinterpret_cast<const bf8v*>(st + th_off + t * 2048);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t0v, q0v, FIRST ? f32x16{} : acc[t], 0, 0,
+        const bf16x8_t t0v = *reinterpret_cast<const bf16x8_t*>(st + th_off + t * 2048);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t0v, q0v, FIRST ? f32x16_t{} : acc[t], 0, 0,
                                                          0);
       }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const bf8v t1v = *reinterpret_cast<const bf8v*>(st + tl_off + t * 2048);
+        const bf16x8_t t1v = *reinterpret_cast<const bf16x8_t*>(st + tl_off + t * 2048);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t1v, q1v, acc[t], 0, 0, 0);
       }
     } else {
-      const h8v qh = *reinterpret_cast<const h8v*>(st + qh_off);
-      const h8v ql = *reinterpret_cast<const h8v*>(st + ql_off);
+      const f16x8_t qh = *reinterpret_cast<const f16x8_t*>(st + qh_off);
+      const f16x8_t ql = *reinterpret_cast<const f16x8_t*>(st + ql_off);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const h8v th = *reinterpret_cast<const h8v*>(st + th_off + t * 2048);
-        const h8v tl = *reinterpret_cast<const h8v*>(st + tl_off + t * 2048);
+        const f16x8_t th = *reinterpret_cast<const f16x8_t*>(st + th_off + t * 2048);
+        const f16x8_t tl = *reinterpret_cast<const f16x8_t*>(st + tl_off + t * 2048);
         // small terms first
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh, FIRST ? f32x16{} : acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh, FIRST ? f32x16_t{} : acc[t], 0, 0, 0);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql, acc[t], 0, 0, 0);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, qh, acc[t], 0, 0, 0);
       }
@@ -2266,7 +2200,7 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(const uint16_t* __restri
   for (int i = 0; i < 4; ++i) {
     const int e = i * 256 + tid;                   // 16-B piece of the workgroup's records
     if (pw + (e >> 2) < N)
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, rec[e]), r,
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, rec[e]), r,
                                              base + (unsigned)e * 16u, 0, 16);
   }
 }

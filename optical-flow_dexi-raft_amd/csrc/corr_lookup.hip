@@ -35,6 +35,7 @@
 #include <type_traits>
 
 #include "dxr_common.h"
+#include "mfma_operands.h"
 #include "out_store.h"
 
 namespace {
@@ -47,6 +48,15 @@ using dxr::store_policy;
 using dxr::NHWC_WRITE_THROUGH;
 using dxr::NHWC_NON_TEMPORAL;
 using dxr::NHWC_PLAIN;
+// MFMA operand types and splits (mfma_operands.h)
+using dxr::f32x16_t;
+using dxr::bf16x8_t;
+using dxr::f16x8_t;
+using dxr::u32x4_t;
+using dxr::u32x2_t;
+using dxr::Bf16Split;
+using dxr::split8_bf16;
+using dxr::split8_f16;
 
 constexpr int FAR_ORIGIN = -(1 << 29);  // window origin of far / non-finite queries
 
@@ -412,7 +422,6 @@ __device__ __forceinline__ void wide_phase0(const float* __restrict__ coords, co
   wide_phase0_taps<R, NT_, QB_, XPITCH>(c, A, l, tid, xs, ys, org);
 }
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------
 // Query-minor lookup (round 6).  The wide kernel stages each query's window as
@@ -574,12 +583,10 @@ __device__ __forceinline__ void qm_load_vec_buf(__amdgpu_buffer_rsrc_t rs, int q
     c[0] = __uint_as_float(v[0]); c[1] = __uint_as_float(v[1]);
     c[2] = __uint_as_float(v[2]); c[3] = __uint_as_float(v[3]);
   } else if constexpr (std::is_same_v<PT, _Float16>) {
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
     const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, 0, 0);
     dxr::f16x2_to_f32(v[0], c);       // an out-of-range slot reads zeros: +0.0
     dxr::f16x2_to_f32(v[1], c + 2);
   } else {
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
     const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, 0, 0);
     c[0] = __uint_as_float(v[0] << 16); c[1] = __uint_as_float(v[0] & 0xffff0000u);
     c[2] = __uint_as_float(v[1] << 16); c[3] = __uint_as_float(v[1] & 0xffff0000u);
@@ -1336,8 +1343,6 @@ int launch_lookup(const PT* pyr, const float* coords, OT* out, const LookupGeom&
 // [plane][k/8][Cout] uint4, hot in L2), bias + ReLU in registers, coalesced
 // 128-B stores along queries into [B, Cout, H, W].
 // ---------------------------------------------------------------------------
-typedef __bf16 mbf8 __attribute__((ext_vector_type(8)));
-typedef float mf16 __attribute__((ext_vector_type(16)));
 
 template <int R>
 struct MotionCfg {
@@ -1349,15 +1354,6 @@ struct MotionCfg {
   static_assert(C::QB == 32, "one 32-query MFMA column block per workgroup");
 };
 
-// hi / mid / lo bf16 bits of x (each round-to-nearest; x = hi + mid + lo exactly
-// for finite x up to the bf16 range of the residuals).
-__device__ __forceinline__ void split3(float x, uint16_t& h, uint16_t& m, uint16_t& l) {
-  h = dxr::f32_to_bf16(x);
-  const float r1 = __fsub_rn(x, dxr::bf16_to_f32(h));
-  m = dxr::f32_to_bf16(r1);
-  l = dxr::f32_to_bf16(__fsub_rn(r1, dxr::bf16_to_f32(m)));
-}
-
 // The convc1 weight [Cout, Cin] f32 rearranged as [Cin_pad/8][Cout][8] (zero
 // padded): one k step of a lane's A operand is 32 contiguous bytes.  Kept in
 // f32 and split in registers by the fused kernel: 4 bytes per weight streamed
@@ -1365,22 +1361,8 @@ __device__ __forceinline__ void split3(float x, uint16_t& h, uint16_t& m, uint16
 // ~70 GB/s of L2 reads per CU, MI355X_MICROARCH.md "gather into LDS").
 // Round 2: the same [Cin_pad/8][Cout][8] layout twice — f32 (the 3-way bf16
 // fallback's operand) and then f16 pairs (8 x f16 hi, 8 x f16 lo in the same 32
-// bytes: the f16-pair GEMM's operand, split once here instead of per k step).
-__device__ __forceinline__ void lk_split8h(const float (&x)[8], uint4& h, uint4& l) {
-  typedef _Float16 h2t __attribute__((ext_vector_type(2)));
-  typedef float f2t __attribute__((ext_vector_type(2)));
-  uint32_t hh[4], ll[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const f2t v = {x[2 * e], x[2 * e + 1]};
-    hh[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, h2t));
-    const h2t hv = __builtin_bit_cast(h2t, hh[e]);
-    const f2t r = {(x[2 * e] - (float)hv[0]) * 2048.f, (x[2 * e + 1] - (float)hv[1]) * 2048.f};
-    ll[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, h2t));
-  }
-  h = make_uint4(hh[0], hh[1], hh[2], hh[3]);
-  l = make_uint4(ll[0], ll[1], ll[2], ll[3]);
-}
+// bytes: the f16-pair GEMM's operand, dxr::split8_f16, split once by
+// conv1x1_pack_weight_kernel instead of per k step).
 
 // ---------------------------------------------------------------------------
 // Round-2 form: two workgroups per CU.  The r01 kernel staged all four levels'
@@ -1394,7 +1376,6 @@ __device__ __forceinline__ void lk_split8h(const float (&x)[8], uint4& h, uint4&
 // finite re-runs the GEMM on the 3-way bf16 split from the f32 samples and the
 // f32 weight copy.  Samples are the lookup's, bit for bit.
 // ---------------------------------------------------------------------------
-typedef _Float16 mh8 __attribute__((ext_vector_type(8)));
 
 // NHWC (DXR_OUT_NHWC): out is [B, H, W, Cout].  A lane's four consecutive output
 // rows (r & 3) of one query are 16 (float32) / 8 (16-bit) contiguous bytes of that
@@ -1492,7 +1473,7 @@ __global__ __launch_bounds__(NT, 4) void corr_lookup_conv1x1_h2_kernel(
     for (int ob0 = 0; ob0 < nob; ob0 += 8) {   // uniform trip count: barriers inside
       const int ob = ob0 + wob;
       const bool act = ob < nob;
-      mf16 acc, acc2;
+      f32x16_t acc, acc2;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = acc2[r] = 0.f;
       if (act) {
@@ -1517,10 +1498,10 @@ __global__ __launch_bounds__(NT, 4) void corr_lookup_conv1x1_h2_kernel(
           const float xq[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
           if constexpr (M2) {
             uint4 qh4, ql4;
-            lk_split8h(xq, qh4, ql4);
-            const mh8 th = __builtin_bit_cast(mh8, wb[sl][0]), tl = __builtin_bit_cast(mh8, wb[sl][1]);
+            split8_f16(xq, qh4, ql4);
+            const f16x8_t th = __builtin_bit_cast(f16x8_t, wb[sl][0]), tl = __builtin_bit_cast(f16x8_t, wb[sl][1]);
             if (refill) wload(wb[sl], min(ks + PF, kend - 1));
-            const mh8 qh = __builtin_bit_cast(mh8, qh4), ql = __builtin_bit_cast(mh8, ql4);
+            const f16x8_t qh = __builtin_bit_cast(f16x8_t, qh4), ql = __builtin_bit_cast(f16x8_t, ql4);
             acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh, acc2, 0, 0, 0);
             acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql, acc2, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, qh, acc, 0, 0, 0);
@@ -1530,14 +1511,14 @@ __global__ __launch_bounds__(NT, 4) void corr_lookup_conv1x1_h2_kernel(
               const float4 a = __builtin_bit_cast(float4, wb[sl][0]);
               const float4 c = __builtin_bit_cast(float4, wb[sl][1]);
               const float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-              dxr::split8(x, wh, wm, wl);
+              split8_bf16<Bf16Split::GUARD_INF_AND_RANGE>(x, wh, wm, wl);
             }
-            dxr::split8(xq, qh4, qm4, ql4);
+            split8_bf16<Bf16Split::GUARD_INF_AND_RANGE>(xq, qh4, qm4, ql4);
             if (refill) wload(wb[sl], min(ks + PF, kend - 1));
-            const mbf8 th = __builtin_bit_cast(mbf8, wh), tm = __builtin_bit_cast(mbf8, wm),
-                       tl = __builtin_bit_cast(mbf8, wl);
-            const mbf8 qh = __builtin_bit_cast(mbf8, qh4), qm = __builtin_bit_cast(mbf8, qm4),
-                       ql = __builtin_bit_cast(mbf8, ql4);
+            const bf16x8_t th = __builtin_bit_cast(bf16x8_t, wh), tm = __builtin_bit_cast(bf16x8_t, wm),
+                       tl = __builtin_bit_cast(bf16x8_t, wl);
+            const bf16x8_t qh = __builtin_bit_cast(bf16x8_t, qh4), qm = __builtin_bit_cast(bf16x8_t, qm4),
+                       ql = __builtin_bit_cast(bf16x8_t, ql4);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tm, qm, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tl, qh, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(th, ql, acc, 0, 0, 0);
@@ -2021,7 +2002,7 @@ extern "C" int64_t dxr_conv1x1_packed_bytes(int64_t cout, int64_t cin) {
 }
 
 namespace {
-// dxr_conv1x1_pack_weight (layout: above, at lk_split8h).
+// dxr_conv1x1_pack_weight (layout: above, under MotionCfg).
 __global__ __launch_bounds__(256) void conv1x1_pack_weight_kernel(const float* __restrict__ w,
                                                                   int cout, int cin, int kbw,
                                                                   float4* __restrict__ packed) {
@@ -2037,7 +2018,7 @@ __global__ __launch_bounds__(256) void conv1x1_pack_weight_kernel(const float* _
   packed[2LL * u] = make_float4(x[0], x[1], x[2], x[3]);
   packed[2LL * u + 1] = make_float4(x[4], x[5], x[6], x[7]);
   uint4 h, l;
-  lk_split8h(x, h, l);
+  split8_f16(x, h, l);
   uint4* pairs = reinterpret_cast<uint4*>(packed + 2LL * kbw * cout);
   pairs[2LL * u] = h;
   pairs[2LL * u + 1] = l;

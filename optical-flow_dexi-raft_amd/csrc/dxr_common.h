@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "dexiraft_corr.h"
+#include "mfma_operands.h"
 
 namespace dxr {
 
@@ -193,80 +194,6 @@ __host__ __device__ __forceinline__ long long cell_index(const LevelLayout& y, i
                                                         int cx) {
   const long long page = (((long long)b * y.qt + q / y.qb) * y.ty + cy / y.th) * y.tx + cx / y.tw;
   return y.off + (page * y.qb + q % y.qb) * (y.th * y.tw) + (cy % y.th) * y.tw + cx % y.tw;
-}
-
-__device__ __forceinline__ float bf16_to_f32(uint16_t v) {
-  return __uint_as_float(((uint32_t)v) << 16);
-}
-
-// Round-to-nearest-even f32 -> bf16 that keeps NaN a NaN.
-__device__ __forceinline__ uint16_t f32_to_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-// Float16 pyramid cells (DXR_PYR_F16).  The element type is _Float16, distinct
-// from the uint16_t of bfloat16 pyramids, so templates pick the conversion by
-// type.  Widening is the hardware v_cvt_f32_f16 (exact, subnormals included).
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void f16x2_to_f32(uint32_t w, float* v) {
-  const f16x2_t h = __builtin_bit_cast(f16x2_t, w);
-  v[0] = (float)h[0];
-  v[1] = (float)h[1];
-}
-
-// Round-to-nearest-even f32 -> f16 (v_cvt_f16_f32: overflow to +-inf, subnormals
-// kept, NaN stays NaN); torch's .half().  The packed v_cvt_pkrtz_f16_f32 rounds
-// toward zero and must not be used for stored cells.  The value is pinned as an
-// f32 register first so that no producing multiply-add is folded into a
-// single-rounding mixed-precision instruction.
-__device__ __forceinline__ uint16_t f32_to_f16_bits(float f) {
-  asm volatile("" : "+v"(f));
-  return __builtin_bit_cast(uint16_t, (_Float16)f);
-}
-__device__ __forceinline__ uint32_t cvt_pk_f16_rne(float a, float b) {
-  return (uint32_t)f32_to_f16_bits(a) | ((uint32_t)f32_to_f16_bits(b) << 16);
-}
-
-// Exact hi/mid/lo split of 8 floats into three 8 x bf16 MFMA operands
-// (x = hi + mid + lo; hi and mid round to nearest, lo keeps the residual's top
-// 16 bits).  Used by the bf16 kernels and the three-way bf16 fallback of the f32-class kernels.
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
-  typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
-  typedef float f2_t __attribute__((ext_vector_type(2)));
-  const f2_t v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf2_t));
-}
-
-__device__ __forceinline__ void split8(const float (&x)[8], uint4& h, uint4& m, uint4& l) {
-  uint32_t hh[4], mm[4], ll[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float a = x[2 * e], b = x[2 * e + 1];
-    uint32_t hp = cvt_pk_bf16(a, b);
-    // a finite value that rounds past bf16's largest finite (|x| > ~3.39e38)
-    // keeps its truncation as hi, so the pair stays finite and exact
-    if (__builtin_isinf(__uint_as_float(hp << 16)) && !__builtin_isinf(a))
-      hp = (hp & 0xffff0000u) | (__float_as_uint(a) >> 16);
-    if (__builtin_isinf(__uint_as_float(hp & 0xffff0000u)) && !__builtin_isinf(b))
-      hp = (hp & 0xffffu) | (__float_as_uint(b) & 0xffff0000u);
-    // an infinite hi (an infinite input) keeps mid = lo = 0 (inf - inf would
-    // turn +-inf products into NaN)
-    const float ha = __uint_as_float(hp << 16), hb = __uint_as_float(hp & 0xffff0000u);
-    const float ra = __builtin_isinf(ha) ? 0.f : a - ha, rb = __builtin_isinf(hb) ? 0.f : b - hb;
-    const uint32_t mp = cvt_pk_bf16(ra, rb);
-    const float la = ra - __uint_as_float(mp << 16), lb = rb - __uint_as_float(mp & 0xffff0000u);
-    hh[e] = hp;
-    mm[e] = mp;
-    ll[e] = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-  }
-  h = make_uint4(hh[0], hh[1], hh[2], hh[3]);
-  m = make_uint4(mm[0], mm[1], mm[2], mm[3]);
-  l = make_uint4(ll[0], ll[1], ll[2], ll[3]);
 }
 
 }  // namespace dxr

@@ -47,21 +47,11 @@ __global__ __launch_bounds__(1024) void xp_split_plain_kernel(const float* __res
   if (kb0 == 0) ex[p] = s;
 #pragma unroll
   for (int i = 0; i < 16; ++i) x[i] = __builtin_ldexpf(x[i], s);
-  uint32_t h[8], l[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    h[e] = cvt_pk_f16(x[2 * e], x[2 * e + 1]);
-    const f16x2_t hv = __builtin_bit_cast(f16x2_t, h[e]);
-    f16x2_t lv;
-    lv[0] = (_Float16)__builtin_fmaf((float)hv[0], -1.f, x[2 * e]);
-    lv[1] = (_Float16)__builtin_fmaf((float)hv[1], -1.f, x[2 * e + 1]);
-    l[e] = __builtin_bit_cast(uint32_t, lv);
-  }
+  uint4 rec[4];
+  split16_f16_record(x, rec);
   uint4* dst = sp + ((long long)kb0 * N + p) * 4;
-  dst[0] = make_uint4(h[0], h[1], h[2], h[3]);
-  dst[1] = make_uint4(h[4], h[5], h[6], h[7]);
-  dst[2] = make_uint4(l[0], l[1], l[2], l[3]);
-  dst[3] = make_uint4(l[4], l[5], l[6], l[7]);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) dst[c] = rec[c];
 }
 
 // XP bits: 0 skip the epilogue stores (K loop kept live), 1 skip the MFMAs,
@@ -168,7 +158,7 @@ __global__ __launch_bounds__(2 * NT, 4) void xp_build_dma_kernel(
   const int th_off = DMA_TILE + trow0 * 64 + 16 * (kh ^ kt);
   const int tl_off = DMA_TILE + trow0 * 64 + 16 * ((2 + kh) ^ kt);
 
-  f32x16 acc[4];
+  f32x16_t acc[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -198,17 +188,17 @@ __global__ __launch_bounds__(2 * NT, 4) void xp_build_dma_kernel(
     if constexpr ((XP & 16) == 0)
       if (ks + 2 < nk && (XP & 4) == 0) dma(ks + 2);
     const unsigned char* st = smem + ((XP & 4) ? (ks & 1) : (ks % DMA_RING)) * DMA_STAGE;
-    const h8v qh = *reinterpret_cast<const h8v*>(st + qh_off);
-    const h8v ql = *reinterpret_cast<const h8v*>(st + ql_off);
-    h8v thv[4], tlv[4];
+    const f16x8_t qh = *reinterpret_cast<const f16x8_t*>(st + qh_off);
+    const f16x8_t ql = *reinterpret_cast<const f16x8_t*>(st + ql_off);
+    f16x8_t thv[4], tlv[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      thv[t] = *reinterpret_cast<const h8v*>(st + th_off + t * 2048);
-      tlv[t] = *reinterpret_cast<const h8v*>(st + tl_off + t * 2048);
+      thv[t] = *reinterpret_cast<const f16x8_t*>(st + th_off + t * 2048);
+      tlv[t] = *reinterpret_cast<const f16x8_t*>(st + tl_off + t * 2048);
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const h8v th = thv[t], tl = tlv[t];
+      const f16x8_t th = thv[t], tl = tlv[t];
       // small terms first
       if constexpr ((XP & 2) != 0) {
         acc[t][0] += (float)(th[0] + tl[1] + qh[2] + ql[3]);
@@ -370,11 +360,11 @@ __global__ __launch_bounds__(PX * 16) void xp_split_px_kernel(const float* __res
 #pragma unroll
   for (int i = 0; i < 16; ++i) x[i] = __builtin_ldexpf(x[i], s);
   uint4 rec[4];
-  split_record(x, rec);
+  split16_f16_record(x, rec);
   const unsigned off = (unsigned)((kb0 * N + p) * 64);
 #pragma unroll
   for (int c = 0; c < 4; ++c)   // per-lane 64-B records: partial-line write-through stores
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, rec[c]), rs, off + 16 * c, 0, 16);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, rec[c]), rs, off + 16 * c, 0, 16);
 }
 
 // Persistent form of the DMA build (round 4 experiment): gridDim.x workgroups
@@ -464,7 +454,7 @@ __global__ __launch_bounds__(2 * NT, 4) void xp_build_persist_kernel(
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rt, (lds_void_t*)(st + DMA_TILE + wave * 1024), 16,
                                                vt, so, 0, 0);
     };
-    f32x16 acc[4];
+    f32x16_t acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -481,13 +471,13 @@ __global__ __launch_bounds__(2 * NT, 4) void xp_build_persist_kernel(
       if constexpr ((XP & 16) == 0)
         if (ks + 2 < nk) dma(ks + 2);
       const unsigned char* st = smem + (ks % DMA_RING) * DMA_STAGE;
-      const h8v qh = *reinterpret_cast<const h8v*>(st + qh_off);
-      const h8v ql = *reinterpret_cast<const h8v*>(st + ql_off);
-      h8v thv[4], tlv[4];
+      const f16x8_t qh = *reinterpret_cast<const f16x8_t*>(st + qh_off);
+      const f16x8_t ql = *reinterpret_cast<const f16x8_t*>(st + ql_off);
+      f16x8_t thv[4], tlv[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        thv[t] = *reinterpret_cast<const h8v*>(st + th_off + t * 2048);
-        tlv[t] = *reinterpret_cast<const h8v*>(st + tl_off + t * 2048);
+        thv[t] = *reinterpret_cast<const f16x8_t*>(st + th_off + t * 2048);
+        tlv[t] = *reinterpret_cast<const f16x8_t*>(st + tl_off + t * 2048);
       }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -583,9 +573,9 @@ constexpr int pipe_part_stores(int part) {
 template <int AUX, typename V>
 __device__ __forceinline__ void pipe_put(__amdgpu_buffer_rsrc_t r, unsigned off, const V v) {
   if constexpr (sizeof(V) == 16)
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), r, off, 0, AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), r, off, 0, AUX);
   else if constexpr (sizeof(V) == 8)
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, v), r, off, 0, AUX);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, v), r, off, 0, AUX);
   else if constexpr (sizeof(V) == 4)
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, off, 0, AUX);
   else
@@ -605,7 +595,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t page_rsrc(OT* base, int elems,
 // queries x all four tiles per part, whole query rows at pitch P0.)
 constexpr int P0 = NTGT + 4;     // LDS pitch (floats) of a staged level-0 query row
 template <typename OT, int AUX, int PART>
-__device__ __forceinline__ void pipe_epilogue_part(const f32x16 (&acc)[4], float* wl, OT* pyr,
+__device__ __forceinline__ void pipe_epilogue_part(const f32x16_t (&acc)[4], float* wl, OT* pyr,
                                                    const BuildGeom& g, long long page, int w4,
                                                    int lane, bool en) {
   const int j = lane & 31, h = lane >> 5;
@@ -629,7 +619,7 @@ __device__ __forceinline__ void pipe_epilogue_part(const f32x16 (&acc)[4], float
         const int off = (lane & 31) * 4;
         const float4 x = f4(wl + qq * P0 + off);
         pipe_put<AUX>(rs, (unsigned)(((w4 * 32 + r * 16 + qq) * NTGT + off) * 4),
-                      f32x4v{x.x, x.y, x.z, x.w});
+                      f32x4_t{x.x, x.y, x.z, x.w});
       }
     } else {
 #pragma unroll
@@ -637,7 +627,7 @@ __device__ __forceinline__ void pipe_epilogue_part(const f32x16 (&acc)[4], float
         const int qq = 4 * k + (lane >> 4);
         const int off = (lane & 15) * 8;
         const float4 a = f4(wl + qq * P0 + off), c = f4(wl + qq * P0 + off + 4);
-        u32x4v u;
+        u32x4_t u;
         u.x = (uint32_t)to_out<OT>(a.x) | ((uint32_t)to_out<OT>(a.y) << 16);
         u.y = (uint32_t)to_out<OT>(a.z) | ((uint32_t)to_out<OT>(a.w) << 16);
         u.z = (uint32_t)to_out<OT>(c.x) | ((uint32_t)to_out<OT>(c.y) << 16);
@@ -679,7 +669,7 @@ __device__ __forceinline__ void pipe_epilogue_part(const f32x16 (&acc)[4], float
           const int qq = 8 * k + (lane >> 3);
           const int off = (lane & 7) * 4;
           const float4 x = f4(wl + qq * P1 + off);
-          pipe_put<AUX>(rs, (unsigned)(((w4 * 32 + qq) * 32 + off) * 4), f32x4v{x.x, x.y, x.z, x.w});
+          pipe_put<AUX>(rs, (unsigned)(((w4 * 32 + qq) * 32 + off) * 4), f32x4_t{x.x, x.y, x.z, x.w});
         }
       } else {
 #pragma unroll
@@ -687,7 +677,7 @@ __device__ __forceinline__ void pipe_epilogue_part(const f32x16 (&acc)[4], float
           const int qq = 16 * k + (lane >> 2);
           const int off = (lane & 3) * 8;
           const float4 a = f4(wl + qq * P1 + off), c = f4(wl + qq * P1 + off + 4);
-          u32x4v u;
+          u32x4_t u;
           u.x = (uint32_t)to_out<OT>(a.x) | ((uint32_t)to_out<OT>(a.y) << 16);
           u.y = (uint32_t)to_out<OT>(a.z) | ((uint32_t)to_out<OT>(a.w) << 16);
           u.z = (uint32_t)to_out<OT>(c.x) | ((uint32_t)to_out<OT>(c.y) << 16);
@@ -703,9 +693,9 @@ __device__ __forceinline__ void pipe_epilogue_part(const f32x16 (&acc)[4], float
       const float r2 = h ? l2[1][2] : l2[0][2], r3 = h ? l2[1][3] : l2[0][3];
       const unsigned off = (unsigned)((w4 * 32 * 8 + j * 8 + 4 * h) * (int)sizeof(OT));
       if constexpr (sizeof(OT) == 4) {
-        pipe_put<AUX>(rs, off, f32x4v{r0, r1, r2, r3});
+        pipe_put<AUX>(rs, off, f32x4_t{r0, r1, r2, r3});
       } else {
-        u32x2v w;
+        u32x2_t w;
         w.x = (uint32_t)to_out<OT>(r0) | ((uint32_t)to_out<OT>(r1) << 16);
         w.y = (uint32_t)to_out<OT>(r2) | ((uint32_t)to_out<OT>(r3) << 16);
         pipe_put<AUX>(rs, off, w);
@@ -784,7 +774,7 @@ __global__ __launch_bounds__(2 * NT, 2) void corr_build_pipe_kernel(
   const int th_off = DMA_TILE + trow0 * 64 + 16 * (kh ^ kt);
   const int tl_off = DMA_TILE + trow0 * 64 + 16 * ((2 + kh) ^ kt);
 
-  f32x16 prev[4];                 // the previous unit's pages (unscaled, divided)
+  f32x16_t prev[4];                 // the previous unit's pages (unscaled, divided)
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -841,7 +831,7 @@ __global__ __launch_bounds__(2 * NT, 2) void corr_build_pipe_kernel(
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rt, (lds_void_t*)(st + DMA_TILE + wave * 1024), 16,
                                                vt, so, 0, 0);
     };
-    f32x16 acc[4];
+    f32x16_t acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -868,25 +858,25 @@ __global__ __launch_bounds__(2 * NT, 2) void corr_build_pipe_kernel(
       }
       const unsigned char* st = smem + (ks % DMA_RING) * DMA_STAGE;
       if constexpr (BF) {
-        const bf8v q0v = *reinterpret_cast<const bf8v*>(st + qh_off);
-        const bf8v q1v = *reinterpret_cast<const bf8v*>(st + ql_off);
+        const bf16x8_t q0v = *reinterpret_cast<const bf16x8_t*>(st + qh_off);
+        const bf16x8_t q1v = *reinterpret_cast<const bf16x8_t*>(st + ql_off);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          const bf8v t0v = *reinterpret_cast<const bf8v*>(st + th_off + t * 2048);
+          const bf16x8_t t0v = *reinterpret_cast<const bf16x8_t*>(st + th_off + t * 2048);
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t0v, q0v, acc[t], 0, 0, 0);
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          const bf8v t1v = *reinterpret_cast<const bf8v*>(st + tl_off + t * 2048);
+          const bf16x8_t t1v = *reinterpret_cast<const bf16x8_t*>(st + tl_off + t * 2048);
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t1v, q1v, acc[t], 0, 0, 0);
         }
       } else {
-        const h8v qh = *reinterpret_cast<const h8v*>(st + qh_off);
-        const h8v ql = *reinterpret_cast<const h8v*>(st + ql_off);
+        const f16x8_t qh = *reinterpret_cast<const f16x8_t*>(st + qh_off);
+        const f16x8_t ql = *reinterpret_cast<const f16x8_t*>(st + ql_off);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          const h8v th = *reinterpret_cast<const h8v*>(st + th_off + t * 2048);
-          const h8v tl = *reinterpret_cast<const h8v*>(st + tl_off + t * 2048);
+          const f16x8_t th = *reinterpret_cast<const f16x8_t*>(st + th_off + t * 2048);
+          const f16x8_t tl = *reinterpret_cast<const f16x8_t*>(st + tl_off + t * 2048);
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh, acc[t], 0, 0, 0);
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql, acc[t], 0, 0, 0);
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, qh, acc[t], 0, 0, 0);
@@ -1276,7 +1266,7 @@ __global__ __launch_bounds__(2 * NT, 4) void xp_dma22_kernel(const uint8_t* __re
   const int th_off = DMA_TILE + 2 * tg * 2048 + trow0 * 64 + 16 * (kh ^ kt);
   const int tl_off = DMA_TILE + 2 * tg * 2048 + trow0 * 64 + 16 * ((2 + kh) ^ kt);
 
-  f32x16 acc[2][2];
+  f32x16_t acc[2][2];
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   const int nk = g.D / BKS;
   dma(0);
@@ -1290,19 +1280,19 @@ __global__ __launch_bounds__(2 * NT, 4) void xp_dma22_kernel(const uint8_t* __re
     __builtin_amdgcn_sched_barrier(0);
     if (kk + 2 < nk) dma(kk + 2);
     const unsigned char* st = smem + (kk % DMA_RING) * DMA_STAGE;
-    h8v qh[2], ql[2];
+    f16x8_t qh[2], ql[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      qh[s] = *reinterpret_cast<const h8v*>(st + qh_off + s * 2048);
-      ql[s] = *reinterpret_cast<const h8v*>(st + ql_off + s * 2048);
+      qh[s] = *reinterpret_cast<const f16x8_t*>(st + qh_off + s * 2048);
+      ql[s] = *reinterpret_cast<const f16x8_t*>(st + ql_off + s * 2048);
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      const h8v th = *reinterpret_cast<const h8v*>(st + th_off + u * 2048);
-      const h8v tl = *reinterpret_cast<const h8v*>(st + tl_off + u * 2048);
+      const f16x8_t th = *reinterpret_cast<const f16x8_t*>(st + th_off + u * 2048);
+      const f16x8_t tl = *reinterpret_cast<const f16x8_t*>(st + tl_off + u * 2048);
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        acc[s][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh[s], FIRST ? f32x16{} : acc[s][u], 0, 0, 0);
+        acc[s][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh[s], FIRST ? f32x16_t{} : acc[s][u], 0, 0, 0);
         acc[s][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql[s], acc[s][u], 0, 0, 0);
         acc[s][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, qh[s], acc[s][u], 0, 0, 0);
       }
@@ -1358,7 +1348,7 @@ __global__ __launch_bounds__(2 * NT, 4) void xp_dma22_kernel(const uint8_t* __re
         const int q = 4 * k + (lane >> 4), pc16 = lane & 15;
         const float4 x = f4(wl + q * PQ22 + pc16 * 4);
         epi_put<4>(pb0, pb0 + (long long)(qbase + q) * NTGT + tg * 64 + pc16 * 4,
-                   f32x4v{x.x, x.y, x.z, x.w});
+                   f32x4_t{x.x, x.y, x.z, x.w});
       }
     }
     epi_sync<1>();

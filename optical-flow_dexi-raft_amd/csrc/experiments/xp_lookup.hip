@@ -148,9 +148,8 @@ __global__ __launch_bounds__(512) void xp_lookup_kernel(const PT* __restrict__ p
       const int k = s / (QB / 4), qa = 4 * (s % (QB / 4));
       const float4 v = *reinterpret_cast<const float4*>(cells + k * QB + qa);
       if (q0 + qa + 3 < g.N) {
-        typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-        const u4 w = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z),
-                      __float_as_uint(v.w)};
+        const u32x4_t w = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z),
+                            __float_as_uint(v.w)};
         __builtin_amdgcn_raw_buffer_store_b128(w, ro, (unsigned)(k * g.N + qa) * 4u, 0, 16);
       }
     }
@@ -324,7 +323,7 @@ int xp_shape(const PT* pyr, const float* coords, float* out, const LookupGeom& g
   return dxr::launch_status();
 }
 
-typedef __attribute__((address_space(3))) void xl_lds_void_t;
+using dxr::lds_void_t;
 
 // Round 6: the wide kernel with its window gathers by
 // LDS-DMA (buffer_load ... lds, 16 B per lane) on the f32 paged levels whose
@@ -384,7 +383,7 @@ __global__ __launch_bounds__(NT_) void xp_lookup_dma_kernel(const PT* __restrict
             voff = e * 4u;
           }
         }
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (xl_lds_void_t*)(cells + gw * 4), 16, voff, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(cells + gw * 4), 16, voff, 0, 0, 0);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else if (A.lth == 30) {

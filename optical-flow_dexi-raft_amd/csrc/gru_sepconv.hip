@@ -25,8 +25,13 @@
 // each register quad, so the NHWC gate stores are 16- and 8-byte vectors.
 #include "dexiraft_gru.h"
 #include "dxr_common.h"
+#include "mfma_operands.h"
 
 namespace {
+
+using dxr::f32x16_t;
+using dxr::bf16x8_t;
+using dxr::f16x8_t;
 
 constexpr int64_t G_MAX_HW = 1LL << 22;
 constexpr int64_t G_MAX_N = 65535;          // grid.y limit
@@ -43,9 +48,6 @@ constexpr int G_PAD = 16;                   // bytes added to an LDS pixel row
 #define DXG_TILE64_ABOVE_WGS 768
 #endif
 
-typedef _Float16 mh8 __attribute__((ext_vector_type(8)));
-typedef __bf16 mbf8 __attribute__((ext_vector_type(8)));
-typedef float mf16 __attribute__((ext_vector_type(16)));
 
 // DXR_OK, DXR_EINVAL or DXR_EUNSUPPORTED for the sizes alone.
 inline int geometry_status(int64_t N, int64_t H, int64_t W, int64_t Ch, int64_t Cx) {
@@ -220,13 +222,13 @@ struct GateGeom {
 enum { MODE_ZR = 0, MODE_QH_STATE = 1, MODE_QH_OUT = 2 };
 
 template <bool BF>
-__device__ __forceinline__ mf16 mfma(const uint4& a, const uint4& b, const mf16& acc) {
+__device__ __forceinline__ f32x16_t mfma(const uint4& a, const uint4& b, const f32x16_t& acc) {
   if constexpr (BF)
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mbf8, a),
-                                                   __builtin_bit_cast(mbf8, b), acc, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a),
+                                                   __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
   else
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(mh8, a),
-                                                  __builtin_bit_cast(mh8, b), acc, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a),
+                                                  __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
 }
 
 __device__ __forceinline__ float sigmoidf(float v) { return 1.0f / (1.0f + expf(-v)); }
@@ -271,7 +273,7 @@ __global__ __launch_bounds__(512) void gate_kernel(
   const int ks_n = C / 16, steps = G_TAPS * ks_n;
   const int64_t wstep = 2 * (int64_t)rows;                       // uint4 per step
   const uint4* wp = wpk + (int64_t)kh * rows + ob * G_BLK + j;   // + s * wstep
-  mf16 acc[NPB];
+  f32x16_t acc[NPB];
 #pragma unroll
   for (int pb = 0; pb < NPB; ++pb)
 #pragma unroll

@@ -10,21 +10,9 @@
 #include <type_traits>
 
 #include "dexiraft_corr.h"
+#include "mfma_operands.h"
 
 namespace dxr {
-
-// The 16 bits of a float32 value rounded to OT (_Float16 / __bf16) to nearest even
-// by the hardware conversions (v_cvt_f16_f32: overflow to +-inf, subnormals kept;
-// v_cvt_pk_bf16_f32): torch's .to(dtype) bit for bit.
-template <typename OT>
-__device__ __forceinline__ uint32_t out16_bits(float r) {
-  static_assert(sizeof(OT) == 2, "16-bit output types");
-  // the float32 value as it stands: without this the compiler folds the last fma
-  // and the conversion into v_fma_mixlo_f16, which rounds the exact sum once to
-  // float16 and so breaks ties differently from float32-then-cast
-  asm volatile("" : "+v"(r));
-  return __builtin_bit_cast(uint16_t, static_cast<OT>(r));
-}
 
 // Parity (in elements) of a 2-byte aligned output base.
 template <typename OT>

@@ -21,8 +21,8 @@ error is measured against:
 
 The bound of the f16-pair form (``bound_pair``)
 -----------------------------------------------
-Contract (file comment of corr_backward.hip, DESIGN 3.5 rounds 4 and 5 (i)): an
-operand x runs as hi + lo of X = x 2^s, hi = RNE_f16(X), lo = RNE_f16(X - hi),
+Contract (``dxr::split8_f16_prescaled``, csrc/mfma_operands.h; file comment of
+corr_backward.hip, DESIGN 3.5 rounds 4 and 5 (i)): an operand x runs as hi + lo of X = x 2^s, hi = RNE_f16(X), lo = RNE_f16(X - hi),
 with s chosen by ``scale_for`` from a bound m on |x|: m < 2^e (frexp), s = 14 - e
 clamped to +-125, so |X| < 2^14.  ``bf_of`` / ``bv_of`` restate that and return
 the power of two the scale stands for, P = 2^(14 - s): one per channel and pair
@@ -63,7 +63,7 @@ for the fmap (m = the channel's max |x|), one for all of dV
 
 The bound of the six-product form (``bound_six``)
 -------------------------------------------------
-``dxr_common.h`` ``split8``: x = hi + mid + lo with hi, mid RNE to bfloat16 (8
+``dxr::split8_bf16<GUARD_INF_AND_RANGE>`` (csrc/mfma_operands.h): x = hi + mid + lo with hi, mid RNE to bfloat16 (8
 significand bits) and lo the top 16 bits of the last remainder.  The remainder
 after two 8-bit roundings of a 24-bit significand has at most 8 bits, so lo is
 exact in the normal range; 2^-25 |x| is allowed per operand all the same (what
@@ -326,7 +326,8 @@ def fraction(err: np.ndarray, bound: np.ndarray) -> float:
 
 # --------------------------------------------------------------------------- emulation
 def _pair16(x: np.ndarray, s) -> tuple[np.ndarray, np.ndarray]:
-    """(hi, lo) of x 2^s as float64 values of numpy float16 roundings."""
+    """Mirrors ``dxr::split8_f16_prescaled`` (csrc/mfma_operands.h): (hi, lo) of
+    x 2^s as float64 values of numpy float16 roundings."""
     X = np.ldexp(x.astype(np.float64), s)
     hi = X.astype(np.float16).astype(np.float64)
     lo = (X - hi).astype(np.float16).astype(np.float64)

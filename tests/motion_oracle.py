@@ -21,11 +21,13 @@ half of the k steps (KSPLIT = 2) and their sums are added to the first half's
 through LDS; larger grids run 512 threads, KSPLIT = 1.  ``ksplit_of`` restates
 the rule.
 
-``lk_split8h``: an operand v (weight or sample) runs as hi = RNE_f16(v) and
+``dxr::split8_f16`` (csrc/mfma_operands.h): an operand v (weight or sample) runs
+as hi = RNE_f16(v) and
 lo = RNE_f16((v - hi) 2048), both subtraction and scaling exact in float32.
 Per k step  acc2 += lo_w hi_x,  acc2 += hi_w lo_x,  acc += hi_w hi_x  in float32;
 then acc = fmaf(acc2, 2^-11, acc), the KSPLIT add, the bias add.  A workgroup
-that sees a non-finite sum repeats its GEMM on ``dxr::split8`` (below).
+that sees a non-finite sum repeats its GEMM on
+``dxr::split8_bf16<GUARD_INF_AND_RANGE>`` (below).
 
 The bound of the f16-pair form (``bound_pair``)
 -----------------------------------------------
@@ -70,7 +72,8 @@ least 2^-24, so every product and partial sum is a multiple of 2^-59.
 
 The bound of the bf16 three-way fallback (``bound_six``)
 --------------------------------------------------------
-``dxr::split8``: hi = RNE_bf16(v), mid = RNE_bf16(v - hi), lo = the top 16 bits
+``dxr::split8_bf16<GUARD_INF_AND_RANGE>`` (csrc/mfma_operands.h):
+hi = RNE_bf16(v), mid = RNE_bf16(v - hi), lo = the top 16 bits
 of v - hi - mid.  bfloat16 has 8 significand bits: |v - hi| <= 2^-8 |v| with at
 most 16 significant bits left, |v - hi - mid| <= 2^-16 |v| with at most 8, so lo
 is exact and v = hi + mid + lo while all three are bf16 normals (|v| >= 2^-103:
@@ -268,7 +271,8 @@ def _pad(a: np.ndarray, axis: int, n: int, repeat_last: bool) -> np.ndarray:
 
 
 def split_f16(v: np.ndarray, flush: bool = False):
-    """``lk_split8h``: (hi, lo) as float32 values of float16 roundings."""
+    """Mirrors ``dxr::split8_f16`` (csrc/mfma_operands.h): (hi, lo) as float32
+    values of float16 roundings."""
     with np.errstate(over="ignore", invalid="ignore"):
         hi = v.astype(np.float16).astype(F32)
         lo = ((v - hi) * F32(2048)).astype(np.float16).astype(F32)
@@ -284,7 +288,8 @@ def _bf16_rne(v: np.ndarray) -> np.ndarray:
 
 
 def split_bf16(v: np.ndarray):
-    """``dxr::split8`` for finite |v| below bf16's largest finite value."""
+    """Mirrors ``dxr::split8_bf16<GUARD_INF_AND_RANGE>`` (csrc/mfma_operands.h) for
+    finite |v| below bf16's largest finite value."""
     hi = _bf16_rne(v)
     r1 = v - hi
     mid = _bf16_rne(r1)

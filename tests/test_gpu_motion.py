@@ -166,7 +166,8 @@ def test_fused_fewer_levels(dx, levels, r):
 def test_fused_weight_above_bf16_max_stays_finite(dx):
     """A finite weight that rounds to inf in bf16 (3.4e38 > ~3.396e38) keeps a
     finite hi/mid/lo split (hi = its truncation), so the contraction matches the
-    float64 product instead of turning into inf (dxr_common.h split8)."""
+    float64 product instead of turning into inf (mfma_operands.h
+    split8_bf16<GUARD_INF_AND_RANGE>)."""
     B, D, H, W = 1, 64, 16, 16
     f1 = _t(dg.fmap(100, B, D, H, W) * np.float32(1e-3))
     f2 = _t(dg.fmap(101, B, D, H, W) * np.float32(1e-3))
