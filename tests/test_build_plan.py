@@ -277,6 +277,18 @@ def rows():
     add(rq(F16, B=65535, D=1 << 20, H=1 << 15, W=1 << 15, L=1, lay=NHWC), EUNSUP)
     add(rq(B=3, D=(1 << 62) + 16, H=1, W=1, L=1), EINVAL)
     add(rq(B=1, D=16, H=1 << 40, W=1 << 40, L=1), EINVAL)
+
+    # --- the requests of tests/test_gpu_build_per_cell.py, at its shapes (16-byte
+    # aligned buffers, as torch allocates them): each reaches the kernel its bound is for
+    import build_oracle as bo
+    code = {"f32": F32, "bf16": BF16, "f16": F16}
+    for r in bo.REQUESTS:
+        B, H, W = bo.CASES[r.case]
+        for L in (1, 2, 3, 4) if r in bo.LEVEL_REQUESTS else (4,):
+            add(rq(code[r.operand], NHWC if r.layout == "nhwc" else NCHW, B=B, D=r.D, H=H, W=W, L=L,
+                   pyr=PYR_F16 if r.cells == "f16" else code[r.cells],
+                   algo=EXACT if r.algo == "exact" else AUTO, ws="exact" if r.ws else None),
+                OK, r.path)
     return t
 
 
