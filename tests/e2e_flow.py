@@ -92,23 +92,94 @@ def _conv(x, W, name, pad):
     return F.conv2d(x, W[name + ".weight"], W[name + ".bias"], padding=pad)
 
 
-def update_block(W, net, inp, corr, flow):
-    """BasicUpdateBlock.forward (core/update.py:132-140): (net, mask, delta_flow)."""
-    # BasicMotionEncoder (core/update.py:90-100)
-    cor = F.relu(_conv(corr, W, "encoder.convc1", 0))
-    cor = F.relu(_conv(cor, W, "encoder.convc2", 1))
-    flo = F.relu(_conv(flow, W, "encoder.convf1", 3))
-    flo = F.relu(_conv(flo, W, "encoder.convf2", 1))
-    out = F.relu(_conv(torch.cat([cor, flo], 1), W, "encoder.conv", 1))
-    x = torch.cat([inp, out, flow], 1)
-    # SepConvGRU (core/update.py:46-60): horizontal then vertical pass
-    h = net
+def sepconv_gru(W, h, x):
+    """SepConvGRU.forward (core/update.py:46-60): horizontal then vertical pass."""
     for sfx, pad in (("1", (0, 2)), ("2", (2, 0))):
         hx = torch.cat([h, x], 1)
         z = torch.sigmoid(_conv(hx, W, "gru.convz" + sfx, pad))
         r = torch.sigmoid(_conv(hx, W, "gru.convr" + sfx, pad))
         q = torch.tanh(_conv(torch.cat([r * h, x], 1), W, "gru.convq" + sfx, pad))
         h = (1 - z) * h + z * q
+    return h
+
+
+GRU_NAMES = ("convz1", "convr1", "convq1", "convz2", "convr2", "convq2")
+
+
+def rne_c(a, cname):
+    """float64 tensor -> nearest-even float16 (``"f16"``) or bfloat16 (``"bf16"``),
+    as float64; ``None``: the identity.  Rounded straight from the float64 bits, as
+    tests/gru_oracle.py::rne does (torch's own double -> 16-bit casts go through
+    float32 and round twice).  float16: subnormals kept, 65520 and beyond to +-inf;
+    bfloat16: values inside its normal range."""
+    assert a.dtype == torch.float64
+    if cname is None:
+        return a
+    drop = {"f16": 42, "bf16": 45}[cname]       # float64 keeps 52 fraction bits, c 10 / 7
+    u = a.contiguous().view(torch.int64)        # sign and magnitude: adding rounds |a| up
+    u = (u + (((u >> drop) & 1) + ((1 << (drop - 1)) - 1))) & -(1 << drop)
+    v = u.view(torch.float64)
+    if cname == "f16":
+        sub = torch.round(a * 2.0 ** 24) * 2.0 ** -24       # spacing 2^-24 below 2^-14
+        v = torch.where(a.abs() < 2.0 ** -14, sub, v)
+        v = torch.where(v.abs() >= 65520.0, torch.copysign(torch.full_like(v, float("inf")), a), v)
+    return v
+
+
+def _conv5(a, w, b, axis):
+    """b + the zero-padded 5-tap convolution of a [N, C, H, W] with w [Co, C, 5] along
+    W (axis 0) or H (axis 1), as five shifted matmuls."""
+    N, C, H, Wd = a.shape
+    ap = F.pad(a, (2, 2, 0, 0) if axis == 0 else (0, 0, 2, 2))
+    P = b[None, :, None, None].expand(N, w.shape[0], H, Wd)
+    for t in range(5):
+        sl = ap[:, :, :, t:t + Wd] if axis == 0 else ap[:, :, t:t + H, :]
+        P = P + torch.einsum("oc,nchw->nohw", w[:, :, t], sl)
+    return P
+
+
+def gru16_emulated(h, x, W, cname):
+    """The fused 16-bit GRU's documented roundings (include/dexiraft_gru.h) and nothing
+    else, in float64 torch ops on h's device: what tests/gru_oracle.py::forward
+    computes in numpy.  Weights, hc = rne_c(h), xc = rne_c(x) and rh = rne_c(r h) are
+    rounded to nearest even in c (``cname``: ``"f16"`` / ``"bf16"``; ``None``: no
+    rounding); the state between the two passes, the biases, the gates and the blend
+    are exact.  ``W`` maps ``[gru.]convz1.weight`` ... ``[gru.]convq2.bias``.  Returns
+    float64; no code under test is involved."""
+    pre = "gru." if "gru.convz1.weight" in W else ""
+    h = torch.as_tensor(h).double()
+    xc = rne_c(torch.as_tensor(x).double().to(h.device), cname)
+    for axis in range(2):
+        w, b = [], []
+        for n in GRU_NAMES[3 * axis:3 * axis + 3]:
+            wn = torch.as_tensor(W[pre + n + ".weight"]).to(h.device).double()
+            w.append(rne_c(wn.reshape(wn.shape[0], wn.shape[1], 5), cname))
+            b.append(torch.as_tensor(W[pre + n + ".bias"]).to(h.device).double())
+        a = torch.cat([rne_c(h, cname), xc], 1)
+        z = torch.sigmoid(_conv5(a, w[0], b[0], axis))
+        r = torch.sigmoid(_conv5(a, w[1], b[1], axis))
+        q = torch.tanh(_conv5(torch.cat([rne_c(r * h, cname), xc], 1), w[2], b[2], axis))
+        h = (1.0 - z) * h + z * q
+    return h
+
+
+def update_block(W, net, inp, corr, flow, gru=None, cor=None, record=None):
+    """BasicUpdateBlock.forward (core/update.py:132-140): (net, mask, delta_flow).
+
+    ``gru``: a callable ``(h, x) -> h'`` in place of the float32 SepConvGRU above.
+    ``cor``: ``relu(convc1(corr))`` computed by the caller (``corr`` is then unused).
+    ``record``: called with ``(net, x)``, the GRU's two arguments, before it runs."""
+    # BasicMotionEncoder (core/update.py:90-100)
+    if cor is None:
+        cor = F.relu(_conv(corr, W, "encoder.convc1", 0))
+    cor = F.relu(_conv(cor, W, "encoder.convc2", 1))
+    flo = F.relu(_conv(flow, W, "encoder.convf1", 3))
+    flo = F.relu(_conv(flo, W, "encoder.convf2", 1))
+    out = F.relu(_conv(torch.cat([cor, flo], 1), W, "encoder.conv", 1))
+    x = torch.cat([inp, out, flow], 1)
+    if record is not None:
+        record(net, x)
+    h = sepconv_gru(W, net, x) if gru is None else gru(net, x)
     # FlowHead (core/update.py:13-14) and the mask head (core/update.py:126-129,139)
     delta = _conv(F.relu(_conv(h, W, "flow_head.conv1", 1)), W, "flow_head.conv2", 1)
     mask = 0.25 * _conv(F.relu(_conv(h, W, "mask.0", 1)), W, "mask.2", 0)
@@ -130,12 +201,41 @@ def coords_grid(B, H, W, device):
     return torch.stack([xs, ys])[None].repeat(B, 1, 1, 1)
 
 
-def refine(corr_fn, corr_en, W, ctx, iters=E2E["iters"]):
+def lookup_each(corr_fn, corr_en, coords1, ecoords1, call):
+    """The default ``lookup=`` of ``refine``: one call per block, as core/raft.py:172-173."""
+    return call(corr_fn, coords1), call(corr_en, ecoords1)
+
+
+def lookup_batched(corr_both, _, coords1, ecoords1, call):
+    """``lookup=`` for one batch-2 block over both volumes:
+    ``corr_fn`` is that block (image pair first), ``corr_en`` is unused."""
+    return call(corr_both, torch.cat([coords1, ecoords1])).chunk(2)
+
+
+def refine(corr_fn, corr_en, W, ctx, iters=E2E["iters"], *, gru=None, motion_first=None,
+           upsample=None, lookup=None, record=None):
     """RAFT.forward's iteration (core/raft.py:160-192) with given correlation blocks.
 
     ``corr_fn`` / ``corr_en`` map coords [B,2,H,W] -> [B,324,H,W].  ``ctx`` holds
     net/inp/enet/einp tensors.  Returns (flow_lowres list per iteration,
     final upsampled flow, final edge flow).
+
+    The hooks stand for the substitutions of INTEGRATION.md; each default is the
+    reference's own step, so a call without them computes what it always did.
+      gru           ``(h, x) -> h'`` in place of the float32 SepConvGRU, both streams
+      motion_first  ``(corr_block, coords) -> cor``: lookup + convc1 + ReLU in one
+                    call (``CorrBlock.lookup_conv1x1``); its result goes to convc2
+      upsample      ``(flow, mask) -> flow_up`` in place of ``upsample_flow``
+      lookup        ``(corr_fn, corr_en, coords1, ecoords1, call) -> (image, edge)``:
+                    how the blocks are called; ``call(block, coords)`` is
+                    ``motion_first`` where given and ``block(coords)`` otherwise
+                    (``lookup_each``, the default; ``lookup_batched``; or a function
+                    that passes ``out_dtype`` / ``memory_format``).  A 16-bit result
+                    is widened to the state's dtype before the update block
+      record        ``record(it, stream, net, x, coords, corr)`` once per iteration
+                    (from 0) and stream (``"image"``, ``"edge"``), as they occur:
+                    the GRU's two arguments, the coordinates looked up and what the
+                    lookup (or ``motion_first``) returned for them
     """
     net, inp, enet, einp = ctx["net"], ctx["inp"], ctx["enet"], ctx["einp"]
     B, _, H, Wd = net.shape
@@ -143,19 +243,29 @@ def refine(corr_fn, corr_en, W, ctx, iters=E2E["iters"]):
     coords1 = coords0.clone()
     ecoords0 = coords_grid(B, H, Wd, net.device)
     ecoords1 = ecoords0.clone()
+    lookup = lookup or lookup_each
+    upsample = upsample or upsample_flow
+    call = motion_first or (lambda block, coords: block(coords))
     flows = []
     up = None
-    for _ in range(iters):
-        corr = corr_fn(coords1)
-        ecorr = corr_en(ecoords1)
+    for it in range(iters):
+        corr, ecorr = lookup(corr_fn, corr_en, coords1, ecoords1, call)
         flow = coords1 - coords0
         eflow = ecoords1 - ecoords0
-        net, up_mask, delta_flow = update_block(W, net, inp, corr, flow)
-        enet, _, delta_eflow = update_block(W, enet, einp, ecorr, eflow)
+        steps = []
+        for stream, h, ctx_in, c, fl, cds in (("image", net, inp, corr, flow, coords1),
+                                              ("edge", enet, einp, ecorr, eflow, ecoords1)):
+            rec = None
+            if record is not None:
+                rec = (lambda n, x, s=stream, c=c, cds=cds: record(it, s, n, x, cds, c))
+            c = c.to(h.dtype)
+            steps.append(update_block(W, h, ctx_in, None if motion_first else c, fl, gru=gru,
+                                      cor=c if motion_first else None, record=rec))
+        (net, up_mask, delta_flow), (enet, _, delta_eflow) = steps
         coords1 = coords1 + delta_flow + delta_eflow
         ecoords1 = ecoords1 + delta_eflow
         flows.append(coords1 - coords0)
-        up = upsample_flow(coords1 - coords0, up_mask)
+        up = upsample(coords1 - coords0, up_mask)
     return flows, up, ecoords1 - ecoords0
 
 
