@@ -383,6 +383,81 @@ int dxr_pyramid_pack(const float* level_data, int64_t B, int64_t H, int64_t W,
  * pyr_dtype | DXR_OUT_NHWC (alone or with one dtype flag): `out` is
  * [B, H, W, num_levels*(2r+1)^2], the same elements bit for bit at
  * ((b*H + h)*W + w)*C + c (see DXR_OUT_NHWC), all radii and level counts.
+ *
+ * Lookup kernels by request (the forward lookups: dxr_corr_lookup,
+ * dxr_corr_lookup_conv1x1, dxr_alt_volume_lookup, dxr_alt_corr_lookup / _ws /
+ * _levels_ws).  csrc/lookup_plan.h is this table's implementation: its
+ * plan_lookup(), plan_volume_lookup() and plan_alt_lookup() answer every refusal
+ * and name the translation unit, the kernel, its grid and its store policy
+ * before anything is launched, and tests/test_lookup_plan.py checks them against
+ * these rows one by one on a CPU.  For every request the checks run in the
+ * order written below (a request that is wrong in two ways answers the first),
+ * and B == 0 is DXR_OK before the pointers are looked at.  N = H*W;
+ * "flagged": any of DXR_OUT_F16 / DXR_OUT_BF16 / DXR_OUT_NHWC.
+ *
+ * Pyramid lookup (dxr_corr_lookup; dxr_corr_lookup_conv1x1 below).  Checks: the
+ * flags on pyr_dtype (both dtype flags, another high bit, a flag on a low value
+ * that is no cell type, a 16-bit `out` at an odd address: DXR_EINVAL); levels
+ * (1..8, every level >= 1 x 1, H*W <= 2^30), radius >= 0 and cout >= 1:
+ * DXR_EINVAL; radius > 8 (fused: radius not 3 or 4, more than 4 levels, cout
+ * % 32 != 0, cout > 4096): DXR_EUNSUPPORTED; B > 65535: DXR_EINVAL; B == 0:
+ * DXR_OK; a null pointer, then an unknown unflagged cell type: DXR_EINVAL.
+ *   unit, by the first that matches:
+ *     DXR_OUT_NHWC                      corr_lookup_nhwc.hip
+ *     DXR_PYR_F16 cells                 corr_lookup_pyr16.hip
+ *     DXR_OUT_F16 / DXR_OUT_BF16        corr_lookup_out16.hip
+ *     else                              corr_lookup.hip
+ *   kernel, grid (x, y, z) and NCHW store policy, in every unit.  wg32 =
+ *   ceil(N / QB) * levels * B with QB = 32 (r <= 4) or 16 (r > 4); "large
+ *   misaligned": N % 32 != 0 and B * (level-0 cells per pair, pages padded) *
+ *   cell bytes * 4/3 >= 128 MiB:
+ *     r <= 4, wg32 <= 1024, not large misaligned (one round):
+ *                                       corr_lookup_qm_kernel<256 x 16>
+ *                                       (ceil(N/16), levels, B); non-temporal
+ *                                       stores if N % 32 == 0, else write-through
+ *     else, r <= 4                      corr_lookup_qm_kernel<512 x 32>
+ *                                       (ceil(N/32), levels, B); non-temporal
+ *     else, r > 4                       corr_lookup_qm_kernel<512 x 16>
+ *                                       (ceil(N/16), levels, B); non-temporal
+ *     (channels-last outputs: non-temporal stores in every shape, at compile time)
+ *   dxr_corr_lookup_conv1x1, grid (ceil(N/32), B):
+ *     ceil(N/32) * B <= 256             corr_lookup_conv1x1_h2_kernel<1024>
+ *     else                              corr_lookup_conv1x1_h2_kernel<512>
+ *
+ * Volume lookup (dxr_alt_volume_lookup).  Checks: a negative radius, the flags
+ * on radius (DXR_ALT_VOL_F16 taken off first; then as above, the odd `out`
+ * included): DXR_EINVAL; levels, 0 <= first_level < num_levels, divisor (not 0,
+ * not NaN): DXR_EINVAL; radius > 8: DXR_EUNSUPPORTED; B > 65535: DXR_EINVAL;
+ * B == 0: DXR_OK; a null pointer: DXR_EINVAL.
+ *   unit: DXR_ALT_VOL_F16               corr_lookup_alt_vol16.hip
+ *         else flagged                  corr_lookup_alt_out.hip
+ *         else                          corr_lookup.hip
+ *   kernel: the pyramid lookup's rule over num_levels - first_level levels,
+ *   without the large misaligned exception:
+ *     r <= 4, wg32 <= 1024              corr_lookup_qm_kernel<ALT, 256 x 16>
+ *     else, r <= 4                      corr_lookup_qm_kernel<ALT, 512 x 32>
+ *     else, r > 4                       corr_lookup_qm_kernel<ALT, 512 x 16>
+ *
+ * On-the-fly lookup (dxr_alt_corr_lookup, _ws, _levels_ws).  Checks: a negative
+ * radius, both input flags, the output flags on radius, then n_levels < 1
+ * (_levels_ws), the odd `out`: DXR_EINVAL; levels, n_levels > num_levels, C < 1,
+ * divisor: DXR_EINVAL; radius > 6: DXR_EUNSUPPORTED; B > 65535, C > 2^20:
+ * DXR_EINVAL; B == 0: DXR_OK; a null pointer, then a null level pointer among
+ * the levels computed: DXR_EINVAL.
+ *   unit: DXR_ALT_IN_BF16               alt_corr_inbf16.hip
+ *         DXR_ALT_IN_F16                alt_corr_in16.hip
+ *         else flagged                  alt_corr_out.hip
+ *         else                          alt_corr.hip
+ *   kernel.  "aligned": C % 4 == 0 and fmap1 and every level computed 16-byte
+ *   aligned; "workspace": non-null, 16-byte aligned and at least
+ *   dxr_alt_workspace_bytes for the levels computed (anything less counts as none):
+ *     aligned, C % 16 == 0, C <= 256 (the matrix-core forms, every unit):
+ *       workspace                       alt_bin_*_kernel + alt_corr_mfma_kernel<ordered>
+ *       else                            alt_corr_mfma_kernel<tile order>
+ *     else, with an input or output flag
+ *                                       none: DXR_EUNSUPPORTED
+ *     else, aligned                     alt_corr_kernel<vec>
+ *     else                              alt_corr_kernel<scalar>
  */
 int dxr_corr_lookup(const void* pyramid, int pyr_dtype,
                     int64_t B, int64_t H, int64_t W, int num_levels, int radius,

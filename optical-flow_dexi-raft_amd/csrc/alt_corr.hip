@@ -213,8 +213,12 @@ __global__ __launch_bounds__(256) void alt_corr_kernel(const float* __restrict__
 // cells are walked in chunks of 4 waves x 32*NRB.  The bilinear combination and
 // the output follow the per-query form exactly.
 // ---------------------------------------------------------------------------
-constexpr int TQY = 4, TQX = 8, TQ = TQY * TQX;    // query tile (32 pixels)
-constexpr int ALT_MFMA_C = 256;                    // channels the query planes hold (C <= 256)
+// query tile (TQY x TQX = TQ = 32 pixels) and the channels the query planes hold
+// (C <= ALT_MFMA_C): lookup_plan.h, with the rule that picks the MFMA forms
+using dxr::TQY;
+using dxr::TQX;
+using dxr::TQ;
+using dxr::ALT_MFMA_C;
 
 // The f16 pair split (3 f16 products, cross terms in a second accumulator), as
 // the split build; a chunk whose sums are not finite (an operand beyond f16
@@ -996,8 +1000,8 @@ __global__ __launch_bounds__(256, MINW) void alt_corr_mfma_kernel(const float* _
 // bit-identical to the tile order's.  (A one-workgroup-per-list form ran the
 // whole job on 4 CUs: 76 us per 1080p lookup.)
 // ---------------------------------------------------------------------------
-constexpr int BIN_MAX = 4096;
-constexpr int OB = 64;            // blocks per list
+using dxr::BIN_MAX;   // lookup_plan.h, with the workspace's size
+using dxr::OB;        // blocks per list
 
 struct BinGeom {
   int bsx[8], bsy[8], nbx[8], nby[8];
@@ -1022,23 +1026,9 @@ BinGeom make_bins(int N, const AltGeom& g, int levels) {
   return b;
 }
 
-// Workspace of one list (coordinate set, level): entries int4[NP] | bin ids
-// int[NP] | cnt int[OB][BIN_MAX + 1] | tot int[BIN_MAX + 1] | cost float[OB]
-// (16-B aligned).
-struct OrderWs {
-  long long np, ents, ids, cnt, tot, cost, bytes;   // byte offsets within a list
-};
-__host__ __device__ inline OrderWs order_ws(long long np) {
-  OrderWs w;
-  w.np = np;
-  w.ents = 0;
-  w.ids = w.ents + 16 * np;
-  w.cnt = w.ids + 4 * np;
-  w.tot = w.cnt + 4LL * OB * (BIN_MAX + 1);
-  w.cost = w.tot + 4LL * (BIN_MAX + 1);
-  w.bytes = (w.cost + 4LL * OB + 15) & ~15LL;
-  return w;
-}
+// Workspace of one list (coordinate set, level): dxr::OrderWs (lookup_plan.h).
+using dxr::OrderWs;
+using dxr::order_ws;
 
 struct OrderArgs {
   unsigned char* ws;   // lists [Z][L] of OrderWs.bytes each
@@ -1218,14 +1208,6 @@ __global__ __launch_bounds__(256) void alt_bin_scatter_kernel(const float* __res
     for (long long i = g.N + tid; i < o.np; i += 256) ents[i] = make_int4(-1, 0, 0, 0);
 }
 
-long long alt_order_entries(long long H, long long W) {
-  return ((W + TQX - 1) / TQX) * ((H + TQY - 1) / TQY) * (long long)TQ;
-}
-
-long long alt_order_bytes(long long H, long long W) {
-  return order_ws(alt_order_entries(H, W)).bytes;
-}
-
 // PF: cell loads of the ordered form kept 4 k steps ahead (round 3: with compact boxes the
 // waves wait on L2 latency, 62 % of wave cycles at PF = 1; 1080p 12 lookups 2,033 -> 1,972 us,
 // Sintel 626 -> 612 us in the step).  The tile-order form stays at 1 (its boxes are L1/TA-bound).
@@ -1260,9 +1242,8 @@ int launch_alt_mfma_r(const float* f1, const float* coords, float* out, const Al
   const int xl_ok = (8 % levels == 0 && ((long long)levels * ntiles) % 8 == 0) ? 1 : 0;
   const int XL = xl < 0 ? 0 : (xl & xl_ok);
   const dim3 grid((unsigned)ntiles, (unsigned)levels, (unsigned)Z);
-  if (g.C > ALT_MFMA_C) return DXR_EUNSUPPORTED;
   // f16 pair split (r02, 1080p: 227 vs 275 us for the 3-way bf16 split), 3 workgroups/CU
-  if (ws != nullptr && Z <= 65535) {
+  if (ws != nullptr) {
     OrderArgs o;
     o.ws = static_cast<unsigned char*>(ws);
     o.np = (long long)ntiles * TQ;
@@ -1329,83 +1310,52 @@ int launch_alt_r(const float* f1, const float* coords, float* out, const AltGeom
   return dxr::launch_status();
 }
 
-// OUTX / okind: a flagged request (alt_corr_out.hip).  The MFMA forms implement
-// every flag combination; the VALU forms decline (DXR_EUNSUPPORTED, nothing
-// launched): a caller runs the unflagged call and converts.
-// IN16: float16 operands (alt_corr_in16.hip); the MFMA forms only, as the flags.
-// INBF (with IN16): bfloat16 operands (alt_corr_inbf16.hip).
+// The form the plan names (dxr::plan_alt_form: MFMA ordered on the workspace, MFMA
+// in tile order, or the per-query VALU form, float4 or scalar loads).
+// OUTX / okind: a flagged request (alt_corr_out.hip); IN16: float16 operands
+// (alt_corr_in16.hip); INBF (with IN16): bfloat16 operands (alt_corr_inbf16.hip).
+// The plan sends those to the MFMA forms only.
 template <bool OUTX = false, bool IN16 = false, bool INBF = false>
-int launch_alt(const float* f1, const float* coords, float* out, const AltGeom& g, int levels,
-               int Z, int radius, bool vec, hipStream_t stream, int W1 = 0,
-               void* ord = nullptr, int okind = 0) {
-  // MFMA form: C a multiple of 16 (k16 steps) up to 256, 16-byte aligned rows;
-  // the per-query VALU form otherwise.  With a workspace (`ord`) the queries are
-  // ordered first (alt_bin_*_kernel).
-  if (vec && W1 > 0 && g.C % 16 == 0 && g.C <= ALT_MFMA_C)
-    return dxr::dispatch_radius<6>(radius, [&](auto r) {
+int launch_alt(const float* f1, const float* coords, float* out, const AltGeom& g,
+               const dxr::AltLookupPlan& p, int Z, hipStream_t stream, int W1, void* ws, int okind) {
+  if (dxr::alt_form_is_mfma(p.form))
+    return dxr::dispatch_radius<6>(p.radius, [&](auto r) {
       return launch_alt_mfma_r<decltype(r)::value, 0, 4, 0, OUTX, IN16, INBF>(
-          f1, coords, out, g, levels, Z, W1, stream, ord, -1, okind);
+          f1, coords, out, g, p.levels, Z, W1, stream, p.use_workspace ? ws : nullptr, -1, okind);
     });
-  if constexpr (OUTX || IN16) return DXR_EUNSUPPORTED;
-  // (not discarded above: the flagged units instantiate the VALU forms too, as they always have)
-  return dxr::dispatch_radius<6>(radius, [&](auto r) {
-    return launch_alt_r<decltype(r)::value>(f1, coords, out, g, levels, Z, vec, stream);
+  // (the flagged units instantiate the VALU forms too, as they always have)
+  return dxr::dispatch_radius<6>(p.radius, [&](auto r) {
+    return launch_alt_r<decltype(r)::value>(f1, coords, out, g, p.levels, Z, p.form == dxr::ALT_VALU_VEC,
+                                            stream);
   });
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
-// 1 / d when d is a (normal) power of two — then x * (1 / d) == x / d exactly — else 0.
-float pow2_recip(float d) {
-  int e;
-  const float m = std::frexp(d, &e);
-  return (m == 0.5f && e > -125 && e < 126) ? 1.f / d : 0.f;
-}
-
-// n_levels < 0: every level; else only levels [0, n_levels) of a num_levels-level
-// output (the rest come from dxr_alt_volume_lookup).
+// A planned on-the-fly lookup (a.plan: lookup_plan.h): the geometry and the launch.
+// plan->levels < num_levels: only those levels of a num_levels-level output (the
+// rest come from dxr_alt_volume_lookup).
 // OUTX / okind: a flagged request (launch_alt); `out` then holds what okind says.
 // IN16: DXR_ALT_IN_F16 — fmap1 and fmap2_levels[0] point at float16.
 // INBF (with IN16): DXR_ALT_IN_BF16 — they point at bfloat16.
 template <bool OUTX = false, bool IN16 = false, bool INBF = false>
-int alt_lookup(const float* fmap1, const float* const* fmap2_levels, const float* coords, float* out,
-               int64_t B, int64_t H, int64_t W, int64_t C, int num_levels, int radius,
-               float divisor, void* workspace, int64_t workspace_bytes, hipStream_t stream,
-               int n_levels = -1, int okind = 0) {
-  dxr::Levels L;
-  if (!dxr::make_levels(B, H, W, num_levels, &L)) return DXR_EINVAL;
-  if (n_levels > num_levels || n_levels == 0) return DXR_EINVAL;
-  const int nl = n_levels < 0 ? num_levels : n_levels;
-  if (C < 1 || radius < 0 || !(divisor == divisor) || divisor == 0.f) return DXR_EINVAL;
-  if (radius > 6) return DXR_EUNSUPPORTED;
-  if (H * W > (1LL << 30) || B > 65535 || C > (1 << 20)) return DXR_EINVAL;
-  if (B == 0) return DXR_OK;
-  if (!fmap1 || !fmap2_levels || !coords || !out) return DXR_EINVAL;
-  const int rd = 2 * radius + 1;
+int alt_lookup(const dxr::AltLookupArgs& a, int okind) {
+  const dxr::AltLookupPlan& p = *a.plan;
+  const int rd = 2 * p.radius + 1;
   AltGeom g;
-  g.N = (int)(H * W);
-  g.C = (int)C;
+  g.N = (int)(a.H * a.W);
+  g.C = (int)a.C;
   g.Nc = 1;
-  g.cout = num_levels * rd * rd;
-  g.divisor = divisor;
-  g.div_recip = pow2_recip(divisor);
-  g.f1_bstride = H * W * C;
-  g.coord_zstride = 2 * H * W;
-  g.coord_cstride = H * W;
+  g.cout = a.num_levels * rd * rd;
+  g.divisor = a.divisor;
+  g.div_recip = p.div_recip;
+  g.f1_bstride = a.H * a.W * a.C;
+  g.coord_zstride = 2 * a.H * a.W;
+  g.coord_cstride = a.H * a.W;
   g.coord_qstride = 1;
-  bool vec = (C % 4 == 0) && aligned16(fmap1);
-  for (int l = 0; l < nl; ++l) {
-    if (!fmap2_levels[l]) return DXR_EINVAL;
-    vec = vec && aligned16(fmap2_levels[l]);
-    g.lv[l] = AltLevel{fmap2_levels[l], L.h[l], L.w[l], 1.f / (float)(1 << l), l * rd * rd};
-  }
+  for (int l = 0; l < p.levels; ++l)
+    g.lv[l] = AltLevel{a.fmap2_levels[l], p.L.h[l], p.L.w[l], 1.f / (float)(1 << l), l * rd * rd};
   if constexpr (IN16) g.f16_levels = 1u;
-  void* ord = nullptr;
-  if (workspace != nullptr && aligned16(workspace) &&
-      workspace_bytes >= (long long)B * nl * alt_order_bytes(H, W))
-    ord = workspace;
-  return launch_alt<OUTX, IN16, INBF>(fmap1, coords, out, g, nl, (int)B, radius, vec, stream, (int)W,
-                                      ord, okind);
+  return launch_alt<OUTX, IN16, INBF>(a.fmap1, a.coords, static_cast<float*>(a.out), g, p, (int)a.B,
+                                      a.stream, (int)a.W, a.workspace, okind);
 }
 
 // A unit's whole shim: alt_lookup on its operand type for the request's output
@@ -1413,12 +1363,9 @@ int alt_lookup(const float* fmap1, const float* const* fmap2_levels, const float
 // follow from the form.
 template <unsigned FORMS, bool IN16 = false, bool INBF = false>
 int alt_lookup_forms(const dxr::AltLookupArgs& a) {
-  return dxr::dispatch_out_form<FORMS>(a.out_flag, a.nhwc, a.out, [&](auto* out, auto nhwc) {
+  return dxr::dispatch_out_form<FORMS>(a.plan->out_flag, a.plan->nhwc, a.out, [&](auto* out, auto nhwc) {
     constexpr int okind = dxr::out_kind<std::remove_pointer_t<decltype(out)>, decltype(nhwc)::value>();
-    return alt_lookup<okind != 0, IN16, INBF>(a.fmap1, a.fmap2_levels, a.coords,
-                                              static_cast<float*>(a.out), a.B, a.H, a.W, a.C,
-                                              a.num_levels, a.radius, a.divisor, a.workspace,
-                                              a.workspace_bytes, a.stream, a.n_levels, okind);
+    return alt_lookup<okind != 0, IN16, INBF>(a, okind);
   });
 }
 
@@ -1431,6 +1378,8 @@ int alt_lookup_forms(const dxr::AltLookupArgs& a) {
 #ifndef DXR_TEMPLATES_ONLY
 
 namespace {
+
+bool aligned16(const void* p) { return dxr::aligned16((uintptr_t)p); }
 
 // ---------------------------------------------------------------------------
 // alt_cuda_corr.backward, reference-FFI form (correlation_kernel.cu:122-256,
@@ -1670,7 +1619,11 @@ extern "C" int dxr_alt_corr_forward(const float* fmap1, const float* fmap2, cons
   g.coord_qstride = 2;
   g.lv[0] = AltLevel{fmap2, (int)H2, (int)W2, 1.f, 0};
   const bool vec = (C % 4 == 0) && aligned16(fmap1) && aligned16(fmap2);
-  return launch_alt(fmap1, coords, corr, g, 1, (int)(B * Nc), radius, vec, stream, (int)W1);
+  dxr::AltLookupPlan p{};   // one level, no flags, no workspace: the lookups' form rule
+  p.radius = radius;
+  p.levels = 1;
+  p.form = dxr::alt_form(vec, C, false);
+  return launch_alt(fmap1, coords, corr, g, p, (int)(B * Nc), stream, (int)W1, nullptr, 0);
 }
 
 extern "C" int dxr_alt_corr_backward(const float* fmap1, const float* fmap2, const float* coords,
@@ -2251,28 +2204,32 @@ extern "C" int dxr_alt_coarse_volumes_ws(const float* fmap1, const float* const*
 }
 
 namespace {
-// The three lookup entry points after their own checks: the output flags or-ed
-// onto `radius` (DXR_OUT_F16 / DXR_OUT_BF16 / DXR_OUT_NHWC, low byte: the radius)
-// are split off first — an invalid combination is DXR_EINVAL before anything
-// else — and a flagged request goes to the flagged forms' translation unit.
+// The three lookup entry points: planned once (lookup_plan.h: every check in its
+// order, the unit, the form, whether the workspace is used), then to the unit the
+// plan names.  The level pointers are read between the planner's two halves, once
+// the array is known to hold them.
 int alt_lookup_entry(const float* fmap1, const float* const* fmap2_levels, const float* coords,
                      float* out, int64_t B, int64_t H, int64_t W, int64_t C, int num_levels,
                      int radius, float divisor, void* workspace, int64_t workspace_bytes,
-                     hipStream_t stream, int n_levels) {
-  dxr::AltLookupArgs a{fmap1, fmap2_levels, coords, out, 0, false, B, H, W, C, num_levels, radius,
-                       divisor, workspace, workspace_bytes, stream, n_levels};
-  if (radius >= 0) {
-    const bool in16 = (radius & DXR_ALT_IN_F16) != 0, inbf = (radius & DXR_ALT_IN_BF16) != 0;
-    if (in16 && inbf) return DXR_EINVAL;   // one input dtype
-    a.radius &= ~(DXR_ALT_IN_F16 | DXR_ALT_IN_BF16);
-    if (!dxr::split_out_flags(&a.radius, &a.out_flag, &a.nhwc)) return DXR_EINVAL;
-    if (a.out_flag != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return DXR_EINVAL;
+                     hipStream_t stream, int n_levels, bool levels_call) {
+  dxr::AltLookupRequest r{B, H, W, C, num_levels, n_levels, levels_call, radius, divisor,
+                          (uintptr_t)fmap1, (uintptr_t)fmap2_levels, (uintptr_t)coords,
+                          (uintptr_t)out, {}, (uintptr_t)workspace, workspace_bytes};
+  dxr::AltLookupPlan plan;
+  int st = dxr::plan_alt_args(r, &plan);
+  if (st != DXR_OK || B == 0) return st;
+  for (int l = 0; l < plan.levels; ++l) r.level[l] = (uintptr_t)fmap2_levels[l];
+  st = dxr::plan_alt_form(r, &plan);
+  if (st != DXR_OK) return st;
+  const dxr::AltLookupArgs a{&plan, fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, divisor,
+                             workspace, stream};
+  switch (plan.unit) {
     // 16-bit fmap1 and level 0, with or without output flags
-    if (inbf) return dxr::alt_lookup_inbf16(a);
-    if (in16) return dxr::alt_lookup_in16(a);
-    if (a.out_flag != 0 || a.nhwc) return dxr::alt_lookup_out(a);
+    case dxr::ALT_UNIT_INBF16: return dxr::alt_lookup_inbf16(a);
+    case dxr::ALT_UNIT_IN16: return dxr::alt_lookup_in16(a);
+    case dxr::ALT_UNIT_OUT: return dxr::alt_lookup_out(a);
+    default: return alt_lookup_forms<dxr::FORM_F32>(a);
   }
-  return alt_lookup_forms<dxr::FORM_F32>(a);
 }
 }  // namespace
 
@@ -2281,13 +2238,11 @@ extern "C" int dxr_alt_corr_lookup(const float* fmap1, const float* const* fmap2
                                    int64_t W, int64_t C, int num_levels, int radius,
                                    float divisor, hipStream_t stream) {
   return alt_lookup_entry(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
-                          nullptr, 0, stream, -1);
+                          nullptr, 0, stream, -1, false);
 }
 
 extern "C" int64_t dxr_alt_workspace_bytes(int64_t B, int64_t H, int64_t W, int num_levels) {
-  if (B < 0 || H < 1 || W < 1 || num_levels < 1 || num_levels > 8 || H * W > (1LL << 30))
-    return -1;
-  return B * num_levels * alt_order_bytes(H, W);
+  return dxr::alt_workspace_bytes(B, H, W, num_levels);
 }
 
 extern "C" int dxr_alt_corr_lookup_ws(const float* fmap1, const float* const* fmap2_levels,
@@ -2296,7 +2251,7 @@ extern "C" int dxr_alt_corr_lookup_ws(const float* fmap1, const float* const* fm
                                       float divisor, void* workspace, int64_t workspace_bytes,
                                       hipStream_t stream) {
   return alt_lookup_entry(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
-                          workspace, workspace_bytes, stream, -1);
+                          workspace, workspace_bytes, stream, -1, false);
 }
 
 extern "C" int dxr_alt_corr_lookup_levels_ws(const float* fmap1, const float* const* fmap2_levels,
@@ -2304,15 +2259,8 @@ extern "C" int dxr_alt_corr_lookup_levels_ws(const float* fmap1, const float* co
                                              int64_t W, int64_t C, int num_levels, int n_levels,
                                              int radius, float divisor, void* workspace,
                                              int64_t workspace_bytes, hipStream_t stream) {
-  {   // invalid output flags answer first, as in the other lookups
-    int r = radius & ~(DXR_ALT_IN_F16 | DXR_ALT_IN_BF16), f;
-    bool n;
-    if (radius >= 0 && (radius & DXR_ALT_IN_F16) && (radius & DXR_ALT_IN_BF16)) return DXR_EINVAL;
-    if (radius >= 0 && !dxr::split_out_flags(&r, &f, &n)) return DXR_EINVAL;
-  }
-  if (n_levels < 1) return DXR_EINVAL;
   return alt_lookup_entry(fmap1, fmap2_levels, coords, out, B, H, W, C, num_levels, radius, divisor,
-                          workspace, workspace_bytes, stream, n_levels);
+                          workspace, workspace_bytes, stream, n_levels, true);
 }
 
 #endif  // DXR_TEMPLATES_ONLY

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "dexiraft_corr.h"
+#include "pyramid_layout.h"
 
 namespace dxr {
 
@@ -86,9 +87,6 @@ inline long long bf16_pack_bytes(long long B, long long D, long long H, long lon
   return size_mul(2, align256(size_mul(size_mul(size_mul(B, D), size_mul(H, W)), 2)));
 }
 
-// H * W <= 2^30 without forming a product that could overflow (H, W >= 1).
-inline bool pixels_ok(int64_t H, int64_t W) { return W <= (1LL << 30) / H; }
-
 // dxr_build_workspace_bytes.
 inline int64_t build_workspace_bytes(int in_dtype, int64_t B, int64_t D, int64_t H, int64_t W) {
   if (B < 0 || D < 1 || H < 1 || W < 1 || !pixels_ok(H, W)) return -1;
@@ -98,12 +96,11 @@ inline int64_t build_workspace_bytes(int in_dtype, int64_t B, int64_t D, int64_t
   return dma_workspace_bytes(B, D, H, W);
 }
 
-// The pyramid's geometry exists (the rule of dxr::make_levels): every level at
-// least 1 x 1, at most 8 levels, H * W <= 2^30.
+// The pyramid's geometry exists (dxr::make_levels, pyramid_layout.h): every level
+// at least 1 x 1, at most 8 levels, H * W <= 2^30.
 inline bool levels_ok(int64_t B, int64_t H, int64_t W, int num_levels) {
-  if (B < 0 || H < 1 || W < 1 || num_levels < 1 || num_levels > 8 || !pixels_ok(H, W))
-    return false;
-  return (H >> (num_levels - 1)) >= 1 && (W >> (num_levels - 1)) >= 1;
+  Levels L;
+  return make_levels(B, H, W, num_levels, &L);
 }
 
 // Argument checks shared by the pyramid builds and dxr_corr_volume; DXR_OK:

@@ -87,7 +87,7 @@ struct LookupGeom {
   int N;          // H * W query pixels per pair
   int levels;
   int cout;       // levels * (2r+1)^2
-  int out_nt = 0; // NCHW lookups: non-temporal output stores (launch_lookup_r decides); the channels-last
+  int out_nt = 0; // NCHW lookups: non-temporal output stores (lookup_plan.h decides); the channels-last
                   // forms take their store policy at compile time and do not read it
   int l0 = 0;     // level of blockIdx.y == 0 (the alternate block's volume lookup: its first coarse level)
   float divisor = 1.f, div_recip = 0.f;   // ALT: the alternate block's division of each output
@@ -118,6 +118,19 @@ LevelAddr level_addr(const dxr::LevelLayout& y) {
   a.rw = short_div ? 1.f / a.wm1 : 0.f;   // IEEE host division: rn(1 / (w - 1))
   a.rh = short_div ? 1.f / a.hm1 : 0.f;
   return a;
+}
+
+// The geometry of a pyramid of L's layout at one radius: N, levels, cout and the
+// levels' addressing.  The one fill; callers add what only they set (out_nt, l0,
+// the alternate block's divisor).
+LookupGeom lookup_geom(const dxr::Levels& L, int radius) {
+  const int rd = 2 * radius + 1;
+  LookupGeom g;
+  g.N = L.h[0] * L.w[0];
+  g.levels = L.n;
+  g.cout = L.n * rd * rd;
+  for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
+  return g;
 }
 
 template <typename PT>
@@ -1215,38 +1228,9 @@ int launch_lookup_backward_r(const BwSets& sets, float* gpyr, const LookupGeom& 
   return dxr::launch_status();
 }
 
-// The product's workgroup shape: true = the one-round 256 x 16 shape, false =
-// 512 x 32 (512 x 16 for r > 4).  Shared by the NCHW and the channels-last
-// launchers.
-// Workgroup shape: 512 threads x 32 queries (4 resident per CU), or — when that
-// grid fits in one dispatch round (<= 1024 workgroups: Sintel / Chairs B=1) —
-// 256 threads x 16 queries, the same 16 threads per query in twice the
-// workgroups, so the per-CU load evens out (3.44 -> 6.9 workgroups per CU at
-// Sintel B=1: one CU in four no longer runs a fourth workgroup after the rest).
-// Round 3, same-process A/B (bit-identical): Sintel B=1 8.0 -> 7.4 us, Chairs
-// 5.6 -> 5.2 us; multi-round grids keep 512 x 32 (Sintel B=8 50.4 vs 53.3 us).
-// Output store policy (round 5, same-process A/Bs in the step, scripts/ab_step.py,
-// profiles/r05/experiments/r6e_lookup_output_nt.jsonl): non-temporal stores
-// gained 2-9 % per step wherever a wave stores whole lines (the 512 x 32 shape: 32
-// consecutive queries of a channel = 128 B; Sintel B=8 -2.3 %, KITTI B=8 bf16
-// -5.6 %, Chairs B=4 -8.9 %, Sintel B=2 -2.3 %) and with the 256 x 16 shape
-// (64-B segments) when those are half-line aligned (N % 32 == 0: Sintel B=1 f32
-// -4.0 %, bf16 -4.4 %); with misaligned 64-B segments (KITTI, Chairs at B=1)
-// write-through stores, which L2 merges, were 2-12 % faster — except with a large
-// pyramid (>= 128 MB: KITTI B=1, 286 MB f32 / 143 MB bf16), where the 512 x 32 shape
-// with non-temporal stores beat both (-6.3 % / -3.9 %, r6k); a small one (Chairs
-// B=1, 43 MB, resident anyway) keeps 256 x 16 with write-through (+13 % otherwise).
-template <int R, typename PT>
-bool lookup_one_round(const LookupGeom& g, int B) {
-  using W = WideCfg<R>;
-  const long long wg32 = (long long)((g.N + W::QB - 1) / W::QB) * g.levels * B;
-  const double pyr_bytes = (double)B * g.lv[0].qt * (double)g.lv[0].qstride * sizeof(PT) * (4.0 / 3.0);
-  const bool big_misaligned = g.N % 32 != 0 && pyr_bytes >= 128.0 * (1 << 20);
-  return R <= 4 && wg32 <= 1024 && !big_misaligned;
-}
-
 // The product lookup (round 6): the query-minor kernel with the round-5 shape
-// and output policy (lookup_one_round, above).  One-round grids (256 x 16)
+// and output policy (dxr::lookup_launch, lookup_plan.h: `s` and g.out_nt come
+// from the plan).  One-round grids (256 x 16)
 // load their window vectors with plain global loads, multi-round grids (512 x
 // 32) with range-checked buffer loads (BUF; the loads need no branch).  Same
 // process, in the step (build + 12 lookups, scripts/ab_step.py, outputs checked
@@ -1255,68 +1239,53 @@ bool lookup_one_round(const LookupGeom& g, int B) {
 // 913.1 -> 884.6 / 854.0, 1080p full 2,176 -> 2,170 / 2,149, Chairs 98.2 -> 96.4
 // / 97.4, Sintel B=2 348.2 -> 355.6 / 349.7.  `ONE_QB` / `UNR` / `MULTI_BUF`:
 // experiment knobs (queries per one-round workgroup, phase-2 unroll, buffer loads
-// on multi-round grids); `ONE_BUF`: buffer loads on one-round grids too.  `OT`
+// on multi-round grids; a caller with another QB brings the grid for it);
+// `ONE_BUF`: buffer loads on one-round grids too.  `OT`
 // (deduced from `out`): float, or _Float16 / __bf16 for the 16-bit output stores —
 // same shapes, same out_nt rule.
 template <int R, typename PT, int ONE_QB = 16, int UNR = 1, bool ONE_BUF = false, bool MULTI_BUF = true,
           int XA = 0, int MULTI_NT = 512, int MULTI_QB = 0, typename OT = float>
-int launch_lookup_r(const PT* pyr, const float* coords, OT* out, const LookupGeom& g0, int B,
-                       hipStream_t stream) {
-  using W = WideCfg<R>;
-  LookupGeom g = g0;
-  if (lookup_one_round<R, PT>(g, B)) {
-    g.out_nt = g.N % 32 == 0 ? 1 : 0;
-    const dim3 grid((unsigned)((g.N + ONE_QB - 1) / ONE_QB), (unsigned)g.levels, (unsigned)B);
+int launch_lookup_r(const PT* pyr, const float* coords, OT* out, const LookupGeom& g,
+                    const dxr::LookupLaunch& s, hipStream_t stream) {
+  constexpr int MQB = MULTI_QB ? MULTI_QB : WideCfg<R>::QB;
+  const dim3 grid(s.gx, s.gy, s.gz);
+  if (s.shape == dxr::SHAPE_ONE_ROUND)
     hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 256, ONE_QB, UNR, ONE_BUF, XA, false, OT>), grid,
                        dim3(256), 0, stream, pyr, coords, out, g);
-    return dxr::launch_status();
-  }
-  g.out_nt = 1;
-  constexpr int MQB = MULTI_QB ? MULTI_QB : W::QB;
-  const dim3 grid((unsigned)((g.N + MQB - 1) / MQB), (unsigned)g.levels, (unsigned)B);
-  hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, MULTI_NT, MQB, UNR, MULTI_BUF, XA, false, OT>), grid,
-                     dim3(MULTI_NT), 0, stream, pyr, coords, out, g);
+  else
+    hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, MULTI_NT, MQB, UNR, MULTI_BUF, XA, false, OT>), grid,
+                       dim3(MULTI_NT), 0, stream, pyr, coords, out, g);
   return dxr::launch_status();
 }
 
 // The channels-last lookup (DXR_OUT_NHWC): launch_lookup_r's two workgroup
-// shapes, chosen by the same rule, with the stores along channels.
-// Output store policy: the NCHW rule above was derived for whole or half lines
-// along queries and does not carry over — here a wave instruction covers 256
-// consecutive bytes (128 with 16-bit outputs) of a query's run of K channels,
-// which starts wherever l * K elements into the query's row falls.
-// Rule (same-process A/B in the step, scripts/ab_nhwc_out.py, profiles/r11/nhwc_out/):
-// non-temporal stores in both shapes.  Per step (build + 12 lookups), non-temporal /
-// write-through / plain: Sintel B=1 213.4 / 231.2 / 229.1 us, Sintel B=8 1,357 /
-// 1,431 / 1,398, KITTI B=8 bf16 939 / 1,019 / 1,018, Sintel B=8 float16 outputs
-// 1,328 / 1,383 / 1,354 (A/A spread 1-8 us): as in the NCHW form, outputs that
-// leave the caches keep the pyramid lines of the next lookups resident.
+// shapes, chosen by the same rule, with the stores along channels and the store
+// policy a compile-time argument (non-temporal in both shapes: the measurements
+// stand at dxr::lookup_launch).
 // POL: the experiments target instantiates the other policies for that A/B.
 template <int R, typename PT, typename OT, int POL = NHWC_NON_TEMPORAL>
-int launch_lookup_nhwc_r(const PT* pyr, const float* coords, OT* out, const LookupGeom& g, int B,
-                         hipStream_t stream) {
-  using W = WideCfg<R>;
+int launch_lookup_nhwc_r(const PT* pyr, const float* coords, OT* out, const LookupGeom& g,
+                         const dxr::LookupLaunch& s, hipStream_t stream) {
+  const dim3 grid(s.gx, s.gy, s.gz);
   if constexpr (R <= 4) {   // the one-round shape exists for these radii only
-    if (lookup_one_round<R, PT>(g, B)) {
-      const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)g.levels, (unsigned)B);
+    if (s.shape == dxr::SHAPE_ONE_ROUND) {
       hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 256, 16, 1, false, 0, false, OT, true, POL>), grid,
                          dim3(256), 0, stream, pyr, coords, out, g);
       return dxr::launch_status();
     }
   }
-  const dim3 grid((unsigned)((g.N + W::QB - 1) / W::QB), (unsigned)g.levels, (unsigned)B);
-  hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 512, W::QB, 1, true, 0, false, OT, true, POL>), grid,
-                     dim3(512), 0, stream, pyr, coords, out, g);
+  hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 512, WideCfg<R>::QB, 1, true, 0, false, OT, true, POL>),
+                     grid, dim3(512), 0, stream, pyr, coords, out, g);
   return dxr::launch_status();
 }
 
 template <typename PT, typename OT, bool NHWC = false>
-int launch_lookup(const PT* pyr, const float* coords, OT* out, const LookupGeom& g, int B,
-                  int radius, hipStream_t stream) {
+int launch_lookup(const PT* pyr, const float* coords, OT* out, const LookupGeom& g,
+                  const dxr::LookupLaunch& s, int radius, hipStream_t stream) {
   return dxr::dispatch_radius<8>(radius, [&](auto r) {
     constexpr int R = decltype(r)::value;
-    if constexpr (NHWC) return launch_lookup_nhwc_r<R, PT>(pyr, coords, out, g, B, stream);
-    else return launch_lookup_r<R, PT>(pyr, coords, out, g, B, stream);
+    if constexpr (NHWC) return launch_lookup_nhwc_r<R, PT>(pyr, coords, out, g, s, stream);
+    else return launch_lookup_r<R, PT>(pyr, coords, out, g, s, stream);
   });
 }
 
@@ -1614,18 +1583,13 @@ __global__ __launch_bounds__(NT, 4) void corr_lookup_conv1x1_h2_kernel(
 // 260.6 / 374.1 us, non-temporal 286.1 / 376.9;
 // profiles/r11/nhwc_out/conv_*.json);
 // POL: the experiments target instantiates non-temporal too.
+// The 1024- or the 512-thread form, as the plan says (dxr::conv1x1_launch).
 template <int R, typename PT, typename OT, bool NHWC = false, int POL = NHWC_PLAIN>
 int launch_lookup_conv1x1_r(const PT* pyr, const float* coords, const float4* wpl,
-                            const float* bias, OT* out, const LookupGeom& g, int B, int cout,
-                            int relu, hipStream_t stream) {
-  using C = WideCfg<R, 1024>;
-  if (g.cout > MotionCfg<R>::KP) return DXR_EUNSUPPORTED;
-  const dim3 grid((unsigned)((g.N + C::QB - 1) / C::QB), (unsigned)B);
-  // Grids up to one workgroup per CU (Sintel B=1: 220) run the 1024-thread form
-  // (more waves per workgroup: 24 vs 26 us); larger grids the 512-thread form,
-  // ~76 KB LDS and 128 VGPRs, two workgroups per CU (Sintel B=2: 35 vs 47 us,
-  // KITTI-shape B=8: 136 vs 190 us; r01 kernel 52 / 214 us).
-  if ((long long)grid.x * grid.y <= 256)
+                            const float* bias, OT* out, const LookupGeom& g,
+                            const dxr::LookupLaunch& s, int cout, int relu, hipStream_t stream) {
+  const dim3 grid(s.gx, s.gy);
+  if (s.shape == dxr::SHAPE_CONV_1024)
     hipLaunchKernelGGL((corr_lookup_conv1x1_h2_kernel<R, PT, 1024, 4, OT, NHWC, POL>), grid, dim3(1024), 0,
                        stream, pyr, coords, wpl, bias, out, g, cout, relu);
   else
@@ -1636,196 +1600,98 @@ int launch_lookup_conv1x1_r(const PT* pyr, const float* coords, const float4* wp
 
 template <typename PT, typename OT, bool NHWC = false>
 int launch_lookup_conv1x1(const PT* pyr, const float* coords, const float4* wpl, const float* bias,
-                          OT* out, const LookupGeom& g, int B, int radius, int cout, int relu,
-                          hipStream_t stream) {
+                          OT* out, const LookupGeom& g, const dxr::LookupLaunch& s, int radius,
+                          int cout, int relu, hipStream_t stream) {
   return dxr::dispatch_radius<4, 3>(radius, [&](auto r) {
-    return launch_lookup_conv1x1_r<decltype(r)::value, PT, OT, NHWC>(pyr, coords, wpl, bias, out, g, B,
+    return launch_lookup_conv1x1_r<decltype(r)::value, PT, OT, NHWC>(pyr, coords, wpl, bias, out, g, s,
                                                                     cout, relu, stream);
   });
 }
 
-// dxr_corr_lookup / dxr_corr_lookup_conv1x1 for one output type: the argument
-// checks (before any launch), the geometry and the launch.  OT = float here;
-// _Float16 / __bf16 are instantiated in corr_lookup_out16.hip only — co-compiled
-// with them, several float32-output kernels were allocated two more VGPRs
-// (DESIGN.md §3.11), and the float32 path is to stay the code it was.
+// A planned dxr_corr_lookup / dxr_corr_lookup_conv1x1 (a.plan: lookup_plan.h) for
+// one output type: the geometry and the launch for the plan's cell type.  OT =
+// float here; _Float16 / __bf16 are instantiated in corr_lookup_out16.hip only —
+// co-compiled with them, several float32-output kernels were allocated two more
+// VGPRs, and the float32 path is to stay the code it was.
 // NHWC (channels-last `out`): instantiated in corr_lookup_nhwc.hip only, for
 // every cell and output type.
-// CELLS: the pyramid cell types the including unit instantiates; a pyr_dtype
-// outside them is DXR_EINVAL (the entry points route it to its own unit first).
+// CELLS: the pyramid cell types the including unit instantiates; the plan routes
+// no other to it.
 enum Cells { CELLS_F32_BF16, CELLS_F16, CELLS_ALL };
 
-template <Cells CELLS, typename OT, bool NHWC = false>
-int corr_lookup_impl(const void* pyramid, int pyr_dtype, int64_t B, int64_t H, int64_t W,
-                     int num_levels, int radius, const float* coords, OT* out,
-                     hipStream_t stream) {
-  dxr::Levels L;
-  if (!dxr::make_levels(B, H, W, num_levels, &L)) return DXR_EINVAL;
-  if (radius < 0) return DXR_EINVAL;
-  if (radius > 8) return DXR_EUNSUPPORTED;
-  if (B > 65535 || H * W > (1LL << 30)) return DXR_EINVAL;
-  if (B == 0) return DXR_OK;
-  if (!pyramid || !coords || !out) return DXR_EINVAL;
-  const int rd = 2 * radius + 1;
-  LookupGeom g;
-  g.N = (int)(H * W);
-  g.levels = num_levels;
-  g.cout = num_levels * rd * rd;
-  for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
-  if constexpr (CELLS != CELLS_F32_BF16) {
-    // float16 cells: corr_lookup_pyr16.hip (and only them), corr_lookup_nhwc.hip
-    if (pyr_dtype == DXR_PYR_F16)
-      return launch_lookup<_Float16, OT, NHWC>(static_cast<const _Float16*>(pyramid), coords, out, g,
-                                               (int)B, radius, stream);
-  }
-  if constexpr (CELLS != CELLS_F16) {
-    if (pyr_dtype == DXR_F32)
-      return launch_lookup<float, OT, NHWC>(static_cast<const float*>(pyramid), coords, out, g, (int)B,
-                                            radius, stream);
-    if (pyr_dtype == DXR_BF16)
-      return launch_lookup<uint16_t, OT, NHWC>(static_cast<const uint16_t*>(pyramid), coords, out, g,
-                                               (int)B, radius, stream);
-  }
-  return DXR_EINVAL;
-}
-
-template <Cells CELLS, typename OT, bool NHWC = false>
-int corr_lookup_conv1x1_impl(const void* pyramid, int pyr_dtype, int64_t B, int64_t H, int64_t W,
-                             int num_levels, int radius, const float* coords,
-                             const void* weight_packed, const float* bias, int64_t cout, int relu,
-                             OT* out, hipStream_t stream) {
-  dxr::Levels L;
-  if (!dxr::make_levels(B, H, W, num_levels, &L)) return DXR_EINVAL;
-  if (radius < 0 || cout < 1) return DXR_EINVAL;
-  if (radius != 3 && radius != 4) return DXR_EUNSUPPORTED;
-  if (num_levels > 4 || cout % 32 != 0 || cout > 4096) return DXR_EUNSUPPORTED;
-  if (B > 65535 || H * W > (1LL << 30)) return DXR_EINVAL;
-  if (B == 0) return DXR_OK;
-  if (!pyramid || !coords || !weight_packed || !out) return DXR_EINVAL;
-  const int rd = 2 * radius + 1;
-  LookupGeom g;
-  g.N = (int)(H * W);
-  g.levels = num_levels;
-  g.cout = num_levels * rd * rd;
-  for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
-  const float4* wpl = static_cast<const float4*>(weight_packed);
-  if constexpr (CELLS != CELLS_F32_BF16) {
-    if (pyr_dtype == DXR_PYR_F16)
-      return launch_lookup_conv1x1<_Float16, OT, NHWC>(static_cast<const _Float16*>(pyramid), coords,
-                                                       wpl, bias, out, g, (int)B, radius, (int)cout,
-                                                       relu, stream);
-  }
-  if constexpr (CELLS != CELLS_F16) {
-    if (pyr_dtype == DXR_F32)
-      return launch_lookup_conv1x1<float, OT, NHWC>(static_cast<const float*>(pyramid), coords, wpl,
-                                                    bias, out, g, (int)B, radius, (int)cout, relu,
-                                                    stream);
-    if (pyr_dtype == DXR_BF16)
-      return launch_lookup_conv1x1<uint16_t, OT, NHWC>(static_cast<const uint16_t*>(pyramid), coords,
-                                                       wpl, bias, out, g, (int)B, radius, (int)cout,
-                                                       relu, stream);
-  }
-  return DXR_EINVAL;
-}
-
-// Either of the two on one argument struct (dxr_common.h): what a unit's shim
-// calls for each of its output forms.
 template <Cells CELLS, bool NHWC, typename OT>
 int pyramid_lookup(const dxr::LookupArgs& a, OT* out) {
-  if (a.conv1x1)
-    return corr_lookup_conv1x1_impl<CELLS, OT, NHWC>(a.pyramid, a.pyr_dtype, a.B, a.H, a.W,
-                                                     a.num_levels, a.radius, a.coords,
-                                                     a.weight_packed, a.bias, a.cout, a.relu, out,
-                                                     a.stream);
-  return corr_lookup_impl<CELLS, OT, NHWC>(a.pyramid, a.pyr_dtype, a.B, a.H, a.W, a.num_levels,
-                                           a.radius, a.coords, out, a.stream);
+  const dxr::LookupPlan& p = *a.plan;
+  LookupGeom g = lookup_geom(p.L, p.radius);
+  g.out_nt = p.launch.out_nt;
+  const auto launch = [&](auto* pyr) {
+    using PT = std::remove_const_t<std::remove_pointer_t<decltype(pyr)>>;
+    if (p.conv1x1)
+      return launch_lookup_conv1x1<PT, OT, NHWC>(pyr, a.coords, static_cast<const float4*>(a.weight_packed),
+                                                 a.bias, out, g, p.launch, p.radius, (int)a.cout,
+                                                 a.relu, a.stream);
+    return launch_lookup<PT, OT, NHWC>(pyr, a.coords, out, g, p.launch, p.radius, a.stream);
+  };
+  if constexpr (CELLS != CELLS_F32_BF16) {
+    // float16 cells: corr_lookup_pyr16.hip (and only them), corr_lookup_nhwc.hip
+    if (p.cells == DXR_PYR_F16) return launch(static_cast<const _Float16*>(a.pyramid));
+  }
+  if constexpr (CELLS != CELLS_F16) {
+    if (p.cells == DXR_F32) return launch(static_cast<const float*>(a.pyramid));
+    if (p.cells == DXR_BF16) return launch(static_cast<const uint16_t*>(a.pyramid));
+  }
+  return DXR_EINVAL;
 }
 
 // A unit's whole shim: pyramid_lookup for the request's output form, FORMS being
 // the forms the unit instantiates (out_store.h).
 template <Cells CELLS, unsigned FORMS>
 int pyramid_lookup_forms(const dxr::LookupArgs& a) {
-  return dxr::dispatch_out_form<FORMS>(a.out_flag, a.nhwc, a.out, [&](auto* out, auto nhwc) {
+  return dxr::dispatch_out_form<FORMS>(a.plan->out_flag, a.plan->nhwc, a.out, [&](auto* out, auto nhwc) {
     return pyramid_lookup<CELLS, decltype(nhwc)::value>(a, out);
   });
 }
 
 // The alternate block's coarse levels from their volumes (dxr_alt_coarse_volumes),
-// levels [first, num_levels): launch_lookup_r's shapes and output policy.  OT /
+// levels [first, num_levels): launch_lookup_r's shapes and output policy, as the
+// plan names them (dxr::plan_volume_lookup).  OT /
 // NHWC: the 16-bit and channels-last stores of the product lookup (above), on this
 // call's channel slice of a num_levels-wide output; instantiated in
 // corr_lookup_alt_out.hip only (float, NCHW: here).  PT: the volumes' cell type;
 // _Float16 (DXR_ALT_VOL_F16) is instantiated in corr_lookup_alt_vol16.hip only, for
 // every output form.
 template <int R, typename OT = float, bool NHWC = false, typename PT = float>
-int launch_alt_volume_r(const PT* vol, const float* coords, OT* out, const LookupGeom& g0,
-                        int first, int B, hipStream_t stream) {
-  using W = WideCfg<R>;
-  LookupGeom g = g0;
-  const int nl = g.levels - first;
-  const long long wg32 = (long long)((g.N + W::QB - 1) / W::QB) * nl * B;
-  if constexpr (NHWC) {   // launch_lookup_nhwc_r's two shapes, chosen by the rule below
-    if constexpr (R <= 4) {
-      if (wg32 <= 1024) {
-        const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)nl, (unsigned)B);
-        hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 256, 16, 1, false, 0, true, OT, true>), grid,
-                           dim3(256), 0, stream, vol, coords, out, g);
-        return dxr::launch_status();
-      }
+int launch_alt_volume_r(const PT* vol, const float* coords, OT* out, const LookupGeom& g,
+                        const dxr::LookupLaunch& s, hipStream_t stream) {
+  const dim3 grid(s.gx, s.gy, s.gz);
+  // the channels-last one-round form exists for r <= 4 only (launch_lookup_nhwc_r);
+  // the NCHW units instantiate theirs for every radius, as they always have
+  if constexpr (!NHWC || R <= 4) {
+    if (s.shape == dxr::SHAPE_ONE_ROUND) {
+      hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 256, 16, 1, false, 0, true, OT, NHWC>), grid,
+                         dim3(256), 0, stream, vol, coords, out, g);
+      return dxr::launch_status();
     }
-    const dim3 grid((unsigned)((g.N + W::QB - 1) / W::QB), (unsigned)nl, (unsigned)B);
-    hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 512, W::QB, 1, true, 0, true, OT, true>), grid,
-                       dim3(512), 0, stream, vol, coords, out, g);
-    return dxr::launch_status();
-  } else {
-  if (R <= 4 && wg32 <= 1024) {
-    g.out_nt = g.N % 32 == 0 ? 1 : 0;
-    const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)nl, (unsigned)B);
-    hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 256, 16, 1, false, 0, true, OT>), grid, dim3(256), 0,
-                       stream, vol, coords, out, g);
-    return dxr::launch_status();
   }
-  g.out_nt = 1;
-  const dim3 grid((unsigned)((g.N + W::QB - 1) / W::QB), (unsigned)nl, (unsigned)B);
-  hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 512, W::QB, 1, true, 0, true, OT>), grid, dim3(512), 0,
-                     stream, vol, coords, out, g);
+  hipLaunchKernelGGL((corr_lookup_qm_kernel<R, PT, 512, WideCfg<R>::QB, 1, true, 0, true, OT, NHWC>), grid,
+                     dim3(512), 0, stream, vol, coords, out, g);
   return dxr::launch_status();
-  }
 }
 
-// dxr_alt_volume_lookup after its flags: the checks (before any launch), the
-// geometry and the launch.
+// A planned dxr_alt_volume_lookup (a.plan: lookup_plan.h) for one output form:
+// the geometry and the launch.
 template <typename OT, bool NHWC = false, typename PT = float>
-int alt_volume_lookup_impl(const PT* volumes, const float* coords, OT* out, int64_t B, int64_t H,
-                           int64_t W, int num_levels, int first_level, int radius, float divisor,
-                           hipStream_t stream) {
-  dxr::Levels L;
-  if (!dxr::make_levels(B, H, W, num_levels, &L) || first_level < 0 || first_level >= num_levels)
-    return DXR_EINVAL;
-  if (radius < 0 || !(divisor == divisor) || divisor == 0.f) return DXR_EINVAL;
-  if (radius > 8) return DXR_EUNSUPPORTED;
-  if (B > 65535) return DXR_EINVAL;
-  if (B == 0) return DXR_OK;
-  if (!volumes || !coords || !out) return DXR_EINVAL;
-  const int rd = 2 * radius + 1;
-  LookupGeom g;
-  g.N = (int)(H * W);
-  g.levels = num_levels;
-  g.cout = num_levels * rd * rd;
-  g.l0 = first_level;
-  g.divisor = divisor;
-  {
-    int e;
-    const float m = std::frexp(divisor, &e);
-    g.div_recip = (m == 0.5f && e > -125 && e < 126) ? 1.f / divisor : 0.f;   // exact: a power of two
-  }
-  for (int l = 0; l < L.n; ++l) {
-    g.lv[l] = level_addr(L.lay[l]);
-    g.lv[l].off -= L.off[first_level];
-  }
-  return dxr::dispatch_radius<8>(radius, [&](auto r) {
-    return launch_alt_volume_r<decltype(r)::value, OT, NHWC, PT>(volumes, coords, out, g, first_level,
-                                                                 (int)B, stream);
+int alt_volume_lookup_impl(const dxr::AltVolumeArgs& a, OT* out) {
+  const dxr::VolumeLookupPlan& p = *a.plan;
+  LookupGeom g = lookup_geom(p.L, p.radius);
+  g.out_nt = p.launch.out_nt;
+  g.l0 = a.first_level;
+  g.divisor = a.divisor;
+  g.div_recip = p.div_recip;
+  for (int l = 0; l < p.L.n; ++l) g.lv[l].off -= p.L.off[a.first_level];
+  return dxr::dispatch_radius<8>(p.radius, [&](auto r) {
+    return launch_alt_volume_r<decltype(r)::value, OT, NHWC, PT>(static_cast<const PT*>(a.volumes),
+                                                                 a.coords, out, g, p.launch, a.stream);
   });
 }
 
@@ -1833,10 +1699,8 @@ int alt_volume_lookup_impl(const PT* volumes, const float* coords, OT* out, int6
 // form, FORMS being the forms the unit instantiates (out_store.h).
 template <typename PT, unsigned FORMS>
 int alt_volume_lookup_forms(const dxr::AltVolumeArgs& a) {
-  return dxr::dispatch_out_form<FORMS>(a.out_flag, a.nhwc, a.out, [&](auto* out, auto nhwc) {
-    return alt_volume_lookup_impl<std::remove_pointer_t<decltype(out)>, decltype(nhwc)::value, PT>(
-        static_cast<const PT*>(a.volumes), a.coords, out, a.B, a.H, a.W, a.num_levels, a.first_level,
-        a.radius, a.divisor, a.stream);
+  return dxr::dispatch_out_form<FORMS>(a.plan->out_flag, a.plan->nhwc, a.out, [&](auto* out, auto nhwc) {
+    return alt_volume_lookup_impl<std::remove_pointer_t<decltype(out)>, decltype(nhwc)::value, PT>(a, out);
   });
 }
 
@@ -1851,60 +1715,46 @@ extern "C" int dxr_alt_volume_lookup(const float* volumes, const float* coords, 
                                      int64_t B, int64_t H, int64_t W, int num_levels,
                                      int first_level, int radius, float divisor,
                                      hipStream_t stream) {
-  dxr::AltVolumeArgs a{volumes, coords, out, 0, false, B, H, W, num_levels, first_level, radius,
-                       divisor, stream};
-  // the flags on `radius` first: DXR_ALT_VOL_F16 (float16 volume cells), then the output
-  // flags (DXR_OUT_F16 / DXR_OUT_BF16 / DXR_OUT_NHWC)
-  if (radius >= 0) {
-    const bool vol16 = (radius & DXR_ALT_VOL_F16) != 0;
-    a.radius &= ~DXR_ALT_VOL_F16;
-    if (!dxr::split_out_flags(&a.radius, &a.out_flag, &a.nhwc)) return DXR_EINVAL;
-    if (a.out_flag != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return DXR_EINVAL;
-    if (vol16) return dxr::alt_volume_lookup_vol16(a);
-    if (a.out_flag != 0 || a.nhwc) return dxr::alt_volume_lookup_out(a);
+  const dxr::VolumeLookupRequest r{B, H, W, num_levels, first_level, radius, divisor,
+                                   (uintptr_t)volumes, (uintptr_t)coords, (uintptr_t)out};
+  dxr::VolumeLookupPlan plan;
+  const int st = dxr::plan_volume_lookup(r, &plan);
+  if (st != DXR_OK || B == 0) return st;
+  const dxr::AltVolumeArgs a{&plan, volumes, coords, out, num_levels, first_level, divisor, stream};
+  switch (plan.unit) {
+    case dxr::VOLUME_UNIT_VOL16: return dxr::alt_volume_lookup_vol16(a);
+    case dxr::VOLUME_UNIT_OUT: return dxr::alt_volume_lookup_out(a);
+    default: return alt_volume_lookup_forms<float, dxr::FORM_F32>(a);
   }
-  return alt_volume_lookup_forms<float, dxr::FORM_F32>(a);
 }
 
 namespace {
-// The output flags of dxr_corr_lookup / dxr_corr_lookup_conv1x1 (the dtype flags
-// DXR_OUT_F16 / DXR_OUT_BF16 and the layout flag DXR_OUT_NHWC, or-ed onto a DXR_F32 /
-// DXR_BF16 / DXR_PYR_F16 pyr_dtype): splits them off.  False (DXR_EINVAL) for both
-// dtype flags, any other high bit, a flag on another low value, or a `out` with a
-// dtype flag that is not 2-byte aligned.  Unflagged values pass through to the
-// callers' own checks.
-bool split_out_dtype(int* pyr_dtype, int* out_flag, bool* nhwc, const void* out) {
-  const int hi = *pyr_dtype & ~0xff;
-  *out_flag = 0;
-  *nhwc = false;
-  if (hi == 0) return true;
-  const int dt = hi & ~DXR_OUT_NHWC;
-  if (dt != 0 && dt != DXR_OUT_F16 && dt != DXR_OUT_BF16) return false;
-  const int lo = *pyr_dtype & 0xff;
-  if (lo != DXR_F32 && lo != DXR_BF16 && lo != DXR_PYR_F16) return false;
-  if (dt != 0 && (reinterpret_cast<uintptr_t>(out) & 1)) return false;
-  *pyr_dtype = lo;
-  *out_flag = dt;
-  *nhwc = (hi & DXR_OUT_NHWC) != 0;
-  return true;
-}
-
-// dxr_corr_lookup and dxr_corr_lookup_conv1x1 after their flags: to the unit that
-// instantiates the request's form.
-int lookup_entry(dxr::LookupArgs a) {
-  if (!split_out_dtype(&a.pyr_dtype, &a.out_flag, &a.nhwc, a.out)) return DXR_EINVAL;
-  if (a.nhwc) return dxr::lookup_nhwc(a);   // channels-last: every cell and output type
-  if (a.pyr_dtype == DXR_PYR_F16) return dxr::lookup_pyr16(a);   // float16 cells: every output type
-  if (a.out_flag) return dxr::lookup_out16(a);
-  return pyramid_lookup_forms<CELLS_F32_BF16, dxr::FORM_F32>(a);
+// dxr_corr_lookup and dxr_corr_lookup_conv1x1: planned once (lookup_plan.h), then
+// to the unit that instantiates the request's form.
+int lookup_entry(const void* pyramid, int pyr_dtype, int64_t B, int64_t H, int64_t W, int num_levels,
+                 int radius, const float* coords, bool conv1x1, const void* weight_packed,
+                 const float* bias, int64_t cout, int relu, void* out, hipStream_t stream) {
+  const dxr::LookupRequest r{pyr_dtype, B, H, W, num_levels, radius, conv1x1, cout,
+                             (uintptr_t)pyramid, (uintptr_t)coords, (uintptr_t)weight_packed,
+                             (uintptr_t)out};
+  dxr::LookupPlan plan;
+  const int st = dxr::plan_lookup(r, &plan);
+  if (st != DXR_OK || B == 0) return st;
+  const dxr::LookupArgs a{&plan, pyramid, coords, weight_packed, bias, cout, relu, out, stream};
+  switch (plan.unit) {
+    case dxr::LOOKUP_UNIT_NHWC: return dxr::lookup_nhwc(a);     // channels-last: every cell and output type
+    case dxr::LOOKUP_UNIT_PYR16: return dxr::lookup_pyr16(a);   // float16 cells: every output type
+    case dxr::LOOKUP_UNIT_OUT16: return dxr::lookup_out16(a);
+    default: return pyramid_lookup_forms<CELLS_F32_BF16, dxr::FORM_F32>(a);
+  }
 }
 }  // namespace
 
 extern "C" int dxr_corr_lookup(const void* pyramid, int pyr_dtype, int64_t B, int64_t H,
                                int64_t W, int num_levels, int radius, const float* coords,
                                float* out, hipStream_t stream) {
-  return lookup_entry({pyramid, pyr_dtype, 0, false, B, H, W, num_levels, radius, coords, false,
-                       nullptr, nullptr, 0, 0, out, stream});
+  return lookup_entry(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords, false, nullptr, nullptr,
+                      0, 0, out, stream);
 }
 
 namespace {
@@ -1920,12 +1770,7 @@ int lookup_backward(const BwSets& sets, int64_t B, int64_t H, int64_t W, int num
   if (!grad_pyramid) return DXR_EINVAL;
   for (int i = 0; i < sets.n; ++i)
     if (!sets.coords[i] || !sets.gout[i]) return DXR_EINVAL;
-  const int rd = 2 * radius + 1;
-  LookupGeom g;
-  g.N = (int)(H * W);
-  g.levels = num_levels;
-  g.cout = num_levels * rd * rd;
-  for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
+  const LookupGeom g = lookup_geom(L, radius);
   float* gp = static_cast<float*>(grad_pyramid);
   return dxr::dispatch_radius<8>(radius, [&](auto r) {
     return launch_lookup_backward_r<decltype(r)::value>(sets, gp, g, (int)B, bound_slots, stream);
@@ -1966,9 +1811,7 @@ extern "C" int64_t dxr_lookup_backward_bound_slots(int64_t B, int64_t H, int64_t
   dxr::Levels L;
   if (!dxr::make_levels(B, H, W, num_levels, &L) || radius < 0 || radius > 8) return -1;
   if (B > 65535 || H * W > (1LL << 30)) return -1;
-  LookupGeom g;
-  g.N = (int)(H * W);
-  g.levels = num_levels;
+  const LookupGeom g = lookup_geom(L, radius);
   dim3 d;
   dxr::dispatch_radius<8>(radius, [&](auto r) {
     d = lookup_backward_grid<decltype(r)::value>(g, (int)B);
@@ -2040,8 +1883,8 @@ extern "C" int dxr_corr_lookup_conv1x1(const void* pyramid, int pyr_dtype, int64
                                        int64_t W, int num_levels, int radius, const float* coords,
                                        const void* weight_packed, const float* bias, int64_t cout,
                                        int relu, float* out, hipStream_t stream) {
-  return lookup_entry({pyramid, pyr_dtype, 0, false, B, H, W, num_levels, radius, coords, true,
-                       weight_packed, bias, cout, relu, out, stream});
+  return lookup_entry(pyramid, pyr_dtype, B, H, W, num_levels, radius, coords, true, weight_packed,
+                      bias, cout, relu, out, stream);
 }
 
 #endif  // DXR_TEMPLATES_ONLY

@@ -22,7 +22,7 @@ extern "C" int dxr_xp_alt_lookup(const float* fmap1, const float* const* fmap2_l
   g.Nc = 1;
   g.cout = num_levels * 81;
   g.divisor = divisor;
-  g.div_recip = pow2_recip(divisor);
+  g.div_recip = dxr::pow2_recip(divisor);
   g.f1_bstride = H * W * C;
   g.coord_zstride = 2 * H * W;
   g.coord_cstride = H * W;

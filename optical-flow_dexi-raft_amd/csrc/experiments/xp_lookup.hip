@@ -283,31 +283,47 @@ __global__ __launch_bounds__(NT_) void corr_lookup_wide_kernel(
   }
 }
 
-// Its round-5 launcher: lookup_one_round's shape rule and the out_nt policy of
-// launch_lookup_r (corr_lookup.hip).
+// The product's shape, grid and store policy for a radius-4 request
+// (dxr::lookup_launch, lookup_plan.h); ONE_QB / MULTI_QB: an experiment's own
+// queries per workgroup in either shape.
+template <typename PT, int ONE_QB = 16, int MULTI_QB = 32>
+dxr::LookupLaunch xp_product_launch(const LookupGeom& g, int B, bool nhwc = false) {
+  dxr::LookupLaunch s = dxr::lookup_launch(4, g.N, g.levels, B, (int)sizeof(PT),
+                                           (int64_t)g.lv[0].qt * g.lv[0].qstride, nhwc);
+  const int qb = s.shape == dxr::SHAPE_ONE_ROUND ? ONE_QB : MULTI_QB;
+  s.gx = (unsigned)((g.N + qb - 1) / qb);
+  return s;
+}
+
+// The wide kernel's round-5 launcher: the product's shape rule and out_nt policy.
 template <int R, typename PT>
 int launch_lookup_wide_r(const PT* pyr, const float* coords, float* out, const LookupGeom& g0, int B,
                     hipStream_t stream) {
-  using W = WideCfg<R>;
+  static_assert(R == 4, "xp_product_launch plans radius 4");
   LookupGeom g = g0;
-  const long long wg32 = (long long)((g.N + W::QB - 1) / W::QB) * g.levels * B;
-  // pyramid bytes as the build's store rule counts them (dma_stream_out): padded
-  // level-0 pages (qt x 128 queries x whole tiles), x 4/3 for levels 1-3
-  const double pyr_bytes = (double)B * g.lv[0].qt * (double)g.lv[0].qstride * sizeof(PT) * (4.0 / 3.0);
-  const bool big_misaligned = g.N % 32 != 0 && pyr_bytes >= 128.0 * (1 << 20);
-  if (R <= 4 && wg32 <= 1024 && !big_misaligned) {
-    using S = WideCfg<R, 256, 16>;
-    g.out_nt = g.N % 32 == 0 ? 1 : 0;
-    const dim3 grid((unsigned)((g.N + S::QB - 1) / S::QB), (unsigned)g.levels, (unsigned)B);
+  const dxr::LookupLaunch s = xp_product_launch<PT>(g, B);
+  g.out_nt = s.out_nt;
+  const dim3 grid(s.gx, s.gy, s.gz);
+  if (s.shape == dxr::SHAPE_ONE_ROUND)
     hipLaunchKernelGGL((corr_lookup_wide_kernel<R, PT, 256, 16>), grid, dim3(256), 0, stream, pyr,
                        coords, out, g);
-    return dxr::launch_status();
-  }
-  g.out_nt = 1;
-  const dim3 grid((unsigned)((g.N + W::QB - 1) / W::QB), (unsigned)g.levels, (unsigned)B);
-  hipLaunchKernelGGL((corr_lookup_wide_kernel<R, PT>), grid, dim3(W::NT), 0, stream, pyr, coords,
-                     out, g);
+  else
+    hipLaunchKernelGGL((corr_lookup_wide_kernel<R, PT>), grid, dim3(WideCfg<R>::NT), 0, stream, pyr,
+                       coords, out, g);
   return dxr::launch_status();
+}
+
+// The product lookup (launch_lookup_r) with its experiment knobs, on the
+// product's plan for the request.
+template <typename PT, int ONE_QB, int UNR, bool ONE_BUF, bool MULTI_BUF, int XA = 0, int MULTI_NT = 512,
+          int MULTI_QB = 0>
+int xp_product(const PT* pyr, const float* coords, float* out, const LookupGeom& g0, int B,
+               hipStream_t stream) {
+  LookupGeom g = g0;
+  const dxr::LookupLaunch s = xp_product_launch<PT, ONE_QB, MULTI_QB ? MULTI_QB : 32>(g, B);
+  g.out_nt = s.out_nt;
+  return launch_lookup_r<4, PT, ONE_QB, UNR, ONE_BUF, MULTI_BUF, XA, MULTI_NT, MULTI_QB>(pyr, coords, out,
+                                                                                        g, s, stream);
 }
 
 // The product kernel with another workgroup shape: NT threads x QB queries
@@ -425,22 +441,16 @@ template <typename PT>
 int xp_dma_launch(const PT* pyr, const float* coords, float* out, const LookupGeom& g0, int B,
                   hipStream_t stream) {
   // launch_lookup_r's shape and output policy
-  using W = WideCfg<4>;
   LookupGeom g = g0;
-  const long long wg32 = (long long)((g.N + W::QB - 1) / W::QB) * g.levels * B;
-  const double pyr_bytes = (double)B * g.lv[0].qt * (double)g.lv[0].qstride * sizeof(PT) * (4.0 / 3.0);
-  const bool big_misaligned = g.N % 32 != 0 && pyr_bytes >= 128.0 * (1 << 20);
-  if (wg32 <= 1024 && !big_misaligned) {
-    g.out_nt = g.N % 32 == 0 ? 1 : 0;
-    const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)g.levels, (unsigned)B);
+  const dxr::LookupLaunch s = xp_product_launch<PT>(g, B);
+  g.out_nt = s.out_nt;
+  const dim3 grid(s.gx, s.gy, s.gz);
+  if (s.shape == dxr::SHAPE_ONE_ROUND)
     hipLaunchKernelGGL((xp_lookup_dma_kernel<4, PT, 256, 16>), grid, dim3(256), 0, stream, pyr,
                        coords, out, g);
-    return dxr::launch_status();
-  }
-  g.out_nt = 1;
-  const dim3 grid((unsigned)((g.N + 31) / 32), (unsigned)g.levels, (unsigned)B);
-  hipLaunchKernelGGL((xp_lookup_dma_kernel<4, PT, 512, 32>), grid, dim3(512), 0, stream, pyr,
-                     coords, out, g);
+  else
+    hipLaunchKernelGGL((xp_lookup_dma_kernel<4, PT, 512, 32>), grid, dim3(512), 0, stream, pyr,
+                       coords, out, g);
   return dxr::launch_status();
 }
 
@@ -459,18 +469,18 @@ int xp_dispatch(int xp, const PT* pyr, const float* coords, float* out, const Lo
     // round 6: query-minor staging (corr_lookup_qm_kernel) with the product's
     // shape / output policy; 91: 256 x 32 on one-round grids
     case 89: return launch_lookup_wide_r<4, PT>(pyr, coords, out, g, B, stream);   // the round-5 product
-    case 90: return launch_lookup_r<4, PT, 16, 1, false, false>(pyr, coords, out, g, B, stream);
-    case 91: return launch_lookup_r<4, PT, 32, 1, false, false>(pyr, coords, out, g, B, stream);
+    case 90: return xp_product<PT, 16, 1, false, false>(pyr, coords, out, g, B, stream);
+    case 91: return xp_product<PT, 32, 1, false, false>(pyr, coords, out, g, B, stream);
     case 92: return xp_dma_launch(pyr, coords, out, g, B, stream);   // LDS-DMA gathers
-    case 93: return launch_lookup_r<4, PT, 16, 2, false, false>(pyr, coords, out, g, B, stream);  // phase 2 x2
-    case 94: return launch_lookup_r<4, PT, 16, 1, true, true>(pyr, coords, out, g, B, stream);  // buffer loads
+    case 93: return xp_product<PT, 16, 2, false, false>(pyr, coords, out, g, B, stream);  // phase 2 x2
+    case 94: return xp_product<PT, 16, 1, true, true>(pyr, coords, out, g, B, stream);  // buffer loads
     // multi-round grids at 256 x 32 / 256 x 16 (the product: 512 x 32)
-    case 95: return launch_lookup_r<4, PT, 16, 1, false, true, 0, 256, 32>(pyr, coords, out, g, B, stream);
-    case 96: return launch_lookup_r<4, PT, 16, 1, false, true, 0, 256, 16>(pyr, coords, out, g, B, stream);
+    case 95: return xp_product<PT, 16, 1, false, true, 0, 256, 32>(pyr, coords, out, g, B, stream);
+    case 96: return xp_product<PT, 16, 1, false, true, 0, 256, 16>(pyr, coords, out, g, B, stream);
     // product shapes, timing ablations: no gathers / no output stores / phase 0 only
-    case 97: return launch_lookup_r<4, PT, 16, 1, false, true, 1>(pyr, coords, out, g, B, stream);
-    case 98: return launch_lookup_r<4, PT, 16, 1, false, true, 2>(pyr, coords, out, g, B, stream);
-    case 99: return launch_lookup_r<4, PT, 16, 1, false, true, 4>(pyr, coords, out, g, B, stream);
+    case 97: return xp_product<PT, 16, 1, false, true, 1>(pyr, coords, out, g, B, stream);
+    case 98: return xp_product<PT, 16, 1, false, true, 2>(pyr, coords, out, g, B, stream);
+    case 99: return xp_product<PT, 16, 1, false, true, 4>(pyr, coords, out, g, B, stream);
     case 0: return xp_launch<0>(pyr, coords, out, g, B, trace, stream);
     case 1: return xp_launch<1>(pyr, coords, out, g, B, trace, stream);
     case 2: return xp_launch<2>(pyr, coords, out, g, B, trace, stream);
@@ -498,11 +508,7 @@ extern "C" int dxr_xp_lookup(const void* pyramid, int pyr_dtype, int64_t B, int6
                              unsigned long long* trace, hipStream_t stream) {
   dxr::Levels L;
   if (!dxr::make_levels(B, H, W, num_levels, &L) || num_levels > 4) return DXR_EINVAL;
-  LookupGeom g;
-  g.N = (int)(H * W);
-  g.levels = num_levels;
-  g.cout = num_levels * 81;
-  for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
+  const LookupGeom g = lookup_geom(L, 4);
   if (pyr_dtype == DXR_F32)
     return xp_dispatch(xp, static_cast<const float*>(pyramid), coords, out, g, (int)B, trace,
                        stream);
@@ -521,31 +527,29 @@ extern "C" int dxr_xp_lookup_nhwc(const void* pyramid, int pyr_dtype, int out_fl
   dxr::Levels L;
   if (!dxr::make_levels(B, H, W, num_levels, &L) || num_levels > 4) return DXR_EINVAL;
   if (out_flag != 0 && out_flag != DXR_OUT_F16) return DXR_EINVAL;
-  LookupGeom g;
-  g.N = (int)(H * W);
-  g.levels = num_levels;
-  g.cout = num_levels * 81;
-  for (int l = 0; l < L.n; ++l) g.lv[l] = level_addr(L.lay[l]);
+  const LookupGeom g = lookup_geom(L, 4);
   auto run = [&](auto* pyr, auto* o) {
     typedef std::remove_const_t<std::remove_pointer_t<decltype(pyr)>> PT;
     typedef std::remove_pointer_t<decltype(o)> OT;
     const float4* wpk = static_cast<const float4*>(weight_packed);
     if (cout == 0) {
+      const dxr::LookupLaunch s = xp_product_launch<PT>(g, (int)B, true);
       switch (policy) {
         case NHWC_WRITE_THROUGH:
-          return launch_lookup_nhwc_r<4, PT, OT, NHWC_WRITE_THROUGH>(pyr, coords, o, g, (int)B, stream);
+          return launch_lookup_nhwc_r<4, PT, OT, NHWC_WRITE_THROUGH>(pyr, coords, o, g, s, stream);
         case NHWC_NON_TEMPORAL:
-          return launch_lookup_nhwc_r<4, PT, OT, NHWC_NON_TEMPORAL>(pyr, coords, o, g, (int)B, stream);
+          return launch_lookup_nhwc_r<4, PT, OT, NHWC_NON_TEMPORAL>(pyr, coords, o, g, s, stream);
         case NHWC_PLAIN:
-          return launch_lookup_nhwc_r<4, PT, OT, NHWC_PLAIN>(pyr, coords, o, g, (int)B, stream);
+          return launch_lookup_nhwc_r<4, PT, OT, NHWC_PLAIN>(pyr, coords, o, g, s, stream);
         default: return (int)DXR_EINVAL;
       }
     }
+    const dxr::LookupLaunch s = dxr::conv1x1_launch(g.N, B);
     if (policy == NHWC_NON_TEMPORAL)
-      return launch_lookup_conv1x1_r<4, PT, OT, true, NHWC_NON_TEMPORAL>(pyr, coords, wpk, bias, o, g, (int)B,
+      return launch_lookup_conv1x1_r<4, PT, OT, true, NHWC_NON_TEMPORAL>(pyr, coords, wpk, bias, o, g, s,
                                                                          (int)cout, 1, stream);
     if (policy == NHWC_PLAIN)
-      return launch_lookup_conv1x1_r<4, PT, OT, true, NHWC_PLAIN>(pyr, coords, wpk, bias, o, g, (int)B,
+      return launch_lookup_conv1x1_r<4, PT, OT, true, NHWC_PLAIN>(pyr, coords, wpk, bias, o, g, s,
                                                                   (int)cout, 1, stream);
     return (int)DXR_EINVAL;
   };

@@ -124,18 +124,6 @@ __device__ __forceinline__ float bf16_nan_as_torch(float r) {
   return r != r ? __uint_as_float(0x7FC00000u) : r;
 }
 
-// The output flags of the lookups (DXR_OUT_F16 / DXR_OUT_BF16 / DXR_OUT_NHWC) or-ed
-// onto an argument whose low byte is the value proper: splits them off.  False
-// for both dtype flags together or any other bit above the low byte.
-inline bool split_out_flags(int* value, int* out_flag, bool* nhwc) {
-  const int hi = *value & ~0xff;
-  const int dt = hi & ~DXR_OUT_NHWC;
-  *out_flag = dt;
-  *nhwc = (hi & DXR_OUT_NHWC) != 0;
-  *value &= 0xff;
-  return dt == 0 || dt == DXR_OUT_F16 || dt == DXR_OUT_BF16;
-}
-
 // The six output forms (element type x layout) as a bit set: the forms a
 // translation unit may instantiate.
 enum : unsigned {
